@@ -58,6 +58,9 @@ def parse_args(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N>1 code path (process group, exchange step, barriers) even with one rank: a self-check")
     ap.add_argument("--stages", action="store_true", help="also print a per-stage HIP-event breakdown to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the output of the last timed headline step (what the caller of the forward receives) as "
+                         "DIR/out.npy, float32; inputs are seeded, so two builds can be compared output for output")
     return ap.parse_args(argv)
 
 
@@ -400,10 +403,11 @@ def worker(args) -> int:
     sub_cap = 200   # steps of a sub-record
     ops.profile_enable(1, (max(args.steps, sub_cap) + 2) * (8 if multi else 1), stride=NO_SAMPLES)
 
-    def measure(step, steps, warmup, launches=1):
+    def measure(step, steps, warmup, launches=1, keep=None):
         """W untimed steps, then exactly K steps between fences; HIP events around block_attn on the launch stream for
         a sample of the steps (an event pair costs stream time, so the stride keeps >= 80 % of the steps bare).
-        Returns (elapsed s, mean block_attn ms per step, event samples)."""
+        Returns (elapsed s, mean block_attn ms per step, event samples); ``keep``: a dict that receives the last timed
+        step's output as a host float32 tensor (copied after the region)."""
         # 4 ... 32 bracketed steps: an event pair is a barrier packet on either side of the kernel (~4 us of bubble
         # on this stack, tools/event_cost.py), so a 20-step region keeps 16 of its steps bare.  The event pool is the
         # process-wide one made at start-up: creating or destroying hundreds of events takes the host milliseconds,
@@ -417,8 +421,9 @@ def worker(args) -> int:
         ops.profile_stride(call_stride)
         fence()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        out = step()
         fence()
         elapsed = time.perf_counter() - t0
         stage_ms, n_rec = ops.profile_read()
@@ -427,6 +432,8 @@ def worker(args) -> int:
             tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt)
+        if keep is not None:   # (a sharded output may be a view of an exchange buffer the next step writes: copy now)
+            keep["out"] = out.detach().float().cpu()
         return elapsed, stage_ms["block_attn"] / max(n_rec, 1) * launches, n_rec
 
     def measure_median(step, steps, warmup, regions=3):
@@ -739,7 +746,8 @@ def worker(args) -> int:
     sub = sub_records() if not multi else {}
 
     # ---------------------------------------------------------------------------------------------- headline region
-    elapsed, attn_ms, n_rec = measure(step, args.steps, args.warmup, launches_per_step(attn))
+    dumped = {} if args.dump_outputs else None
+    elapsed, attn_ms, n_rec = measure(step, args.steps, args.warmup, launches_per_step(attn), keep=dumped)
     ms_per_step = elapsed / args.steps * 1e3
     exch = None
     if multi:
@@ -816,6 +824,11 @@ def worker(args) -> int:
         if "cpu_baseline" in line:
             summ["cpu_points_per_s"] = line["cpu_baseline"]["value"]
         ordered["summary"] = summ
+        if dumped is not None:   # (every rank holds the gathered output; rank 0 writes it)
+            import numpy as np
+
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "out.npy"), dumped["out"].numpy())
         print(json.dumps(ordered), flush=True)
     if multi:
         with c_stdout_to_stderr():

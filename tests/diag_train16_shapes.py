@@ -1,7 +1,7 @@
 """Diagnostic (not a test): fp32 vs bf16 training tiles on synthetic clouds of several shapes, clustered (cluster_size 8)
 and not: max error / tensor scale and mean error / mean magnitude per tensor.  python tests/diag_train16_shapes.py"""
 import os, sys, torch
-R=os.environ.get("GRAFT_REPO_ROOT","/root/repo")
+R=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (R, R+"/tests", R+"/tests/golden", R+"/oracle"): sys.path.insert(0,p)
 from hept_amd.synthetic import make_inputs
 from test_gpu_backward import _train_once

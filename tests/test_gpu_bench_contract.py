@@ -115,6 +115,26 @@ def test_bench_line(precision, dtype, gpu_device):
     assert 1e7 < d["value"] < 1e10 and abs(d["value"] - 60000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
 
 
+def test_bench_dumps_the_output_of_its_last_timed_step(tmp_path, gpu_device):
+    """--dump-outputs DIR: the headline forward's output (what its caller receives) as DIR/out.npy in float32, equal to
+    the plain operator on the same seeded inputs -- so two builds can be compared output for output."""
+    import numpy as np
+    import torch
+
+    from hept_amd import ops
+    from hept_amd.synthetic import workload_inputs
+
+    d = _run("--no-extra", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump"))
+    assert d["steps"] == 20 and d["ms_per_step"] > 0
+    out = np.load(tmp_path / "dump" / "out.npy")
+    inp = workload_inputs("tracking-60k", seed=0)
+    g = {k: v.to(gpu_device) for k, v in inp.items() if torch.is_tensor(v)}
+    plain = ops.forward(g["q"], g["k"], g["v"], g["coords"], g["combined_shifts"], g["w_rpe_weight"], g["alpha"],
+                        g["out_weight"], g["out_bias"], block_size=128, w_per_dist=10, precision="bf16").cpu()
+    assert out.dtype == np.float32 and out.shape == tuple(plain.shape) and np.isfinite(out).all()
+    torch.testing.assert_close(torch.from_numpy(out), plain, rtol=1e-5, atol=1e-6)
+
+
 def test_bench_line_with_the_exchange_forced_on(gpu_device):
     d = _run("--force-dist", "--no-cpu-baseline")
     assert KEYS <= set(d) and "exchange" in d["config"]["parallelism"] and d["config"]["rccl_ranks"] == 1
@@ -123,7 +143,9 @@ def test_bench_line_with_the_exchange_forced_on(gpu_device):
 @pytest.mark.parametrize("ranks", [2, 8])
 def test_bench_launches_its_own_ranks(ranks, gpu_device):
     """`python bench.py --gpus N` with WORLD_SIZE unset: the parent starts N ranks (here they share the one GPU through
-    a gloo group: RCCL refuses two ranks per device), relays rank 0's line and exits 0."""
+    a gloo group: RCCL refuses two ranks per device), relays rank 0's line and exits 0.  (The 8-GPU case runs 4 ranks
+    here: a GPU machine takes at most 6 processes with a device open at once, and this pytest process holds one too.)"""
+    ranks = min(ranks, 4)
     # (HEPT_EXCHANGE=torch: the collectives go through gloo.  The one-sided transport polls arrival flags on the GPU,
     # and N processes polling on ONE shared GPU crawl from time slice to time slice; it is covered on small inputs by
     # tests/test_gpu_two_process.py.)

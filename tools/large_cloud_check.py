@@ -4,7 +4,7 @@ HEPT_NO_STAGED_COMBINE=1: the combine loads its rows lane by lane) must be equal
 several tiles, the only place where the staged rows' cross-tile prefetch runs.
 python tools/large_cloud_check.py [precision]"""
 import sys, os, time, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hept_amd import HEPTAttention
 from hept_amd.synthetic import make_inputs
 dev = torch.device("cuda", 0)
