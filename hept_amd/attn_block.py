@@ -49,8 +49,11 @@ class Attn(nn.Module):
         self._workspace = None
 
     def _fused_ok(self, x) -> bool:
+        # the fused row builder is built for D = 24, H = 8 and C in {6, 4, 2} only (hept_prep_hash_fused_rpe,
+        # csrc/prep_hash.hip); any other shape composes the block around the operator
+        coords_dim = self.attn.e2lsh.alpha.shape[1] - self.dim_per_head
         return (x.is_cuda and not self.training and not torch.is_grad_enabled() and self.dim_per_head == 24
-                and self.num_heads == 8 and self.attn.sharding is None)
+                and self.num_heads == 8 and coords_dim in (2, 4, 6) and self.attn.sharding is None)
 
     # training / grad-enabled calls: LayerNorm + projections + operator as one autograd node (False: compose modules)
     fuse_training = True
