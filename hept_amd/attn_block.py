@@ -13,6 +13,12 @@ the epilogue of the combine kernel.  In training mode (dropout active, gradients
 torch modules exactly like the reference, but ``norm1`` and the three projections are folded into the operator's row
 builder as one autograd node (``autograd.HeptPartialSumsFused``): q, k, v are never written to HBM in the forward, and
 the backward adds the small dense products behind the HIP gradients of the block attention.
+
+``Attn(coords_dim, variant="src", ...)`` wraps the reference's src operator instead (``HEPTAttention(variant="src")``)
+and takes that variant's kwargs (``raw_size``, ``coords``, ``region_indices``, ``regions_h`` from
+``prepare_input_src``) in all three modes: eval is one C call (``hept_attn_block_forward_src``), training folds the front
+end into the row builder the same way.  ``SrcAttn`` is the drop-in for the src block itself
+(``src/models/baselines/transformer.py:160-229``): its constructor, ``attn_type="hept"`` only.
 """
 from __future__ import annotations
 
@@ -22,7 +28,7 @@ import torch.nn as nn
 from . import ops
 from .hept import HEPTAttention
 
-__all__ = ["Attn"]
+__all__ = ["Attn", "SrcAttn"]
 
 
 class Attn(nn.Module):
@@ -81,10 +87,21 @@ class Attn(nn.Module):
                 ff_output = self.ff(self.norm2(x))
             return x + self.dropout(ff_output)
         a = self.attn
+        src = a.variant == "src"
         if torch.compiler.is_compiling():
             # one opaque graph node (hept_amd/library.py) instead of a ctypes call Dynamo cannot trace
-            from .library import attn_block_op
+            from .library import attn_block_op, attn_block_src_op
 
+            if src:
+                eta, phi = kwargs["region_indices"]
+                y = attn_block_src_op(x.float(), kwargs["coords"].float(), eta, phi, kwargs["regions_h"],
+                                      int(kwargs["raw_size"]), self.norm1.weight, self.norm1.bias, self.w_q.weight,
+                                      self.w_k.weight, self.w_v.weight, self.w_rpe.weight, a.e2lsh.alpha,
+                                      a.out_linear.weight, a.out_linear.bias, self.norm2.weight, self.norm2.bias,
+                                      self.ff[0].weight, self.ff[0].bias, self.ff[2].weight, self.ff[2].bias,
+                                      self.num_heads, a.block_size, a.num_w_per_dist, self.norm1.eps, self.norm2.eps,
+                                      a.precision)
+                return y.to(x.dtype)
             y = attn_block_op(x.float(), kwargs["coords"].float(), kwargs["combined_shifts"], self.norm1.weight,
                               self.norm1.bias, self.w_q.weight, self.w_k.weight, self.w_v.weight, self.w_rpe.weight,
                               a.e2lsh.alpha, a.out_linear.weight, a.out_linear.bias, self.norm2.weight,
@@ -109,7 +126,32 @@ class Attn(nn.Module):
             "norm2.bias": self.norm2.bias, "ff.0.weight": self.ff[0].weight, "ff.0.bias": self.ff[0].bias,
             "ff.2.weight": self.ff[2].weight, "ff.2.bias": self.ff[2].bias,
         }
-        y = ops.attn_block_forward(x.float(), kwargs["coords"].float(), kwargs["combined_shifts"], params,
-                                   num_heads=self.num_heads, block_size=a.block_size, w_per_dist=a.num_w_per_dist,
-                                   eps1=self.norm1.eps, eps2=self.norm2.eps, precision=a.precision, workspace=ws)
+        common = dict(num_heads=self.num_heads, block_size=a.block_size, w_per_dist=a.num_w_per_dist,
+                      eps1=self.norm1.eps, eps2=self.norm2.eps, precision=a.precision, workspace=ws)
+        if src:
+            y = ops.attn_block_forward_src(x.float(), kwargs["coords"].float(), kwargs["region_indices"],
+                                           kwargs["regions_h"], kwargs["raw_size"], params, **common)
+        else:
+            y = ops.attn_block_forward(x.float(), kwargs["coords"].float(), kwargs["combined_shifts"], params, **common)
         return y.to(x.dtype)
+
+
+class SrcAttn(Attn):
+    """Drop-in for the src variant's block (reference ``src/models/baselines/transformer.py:160-229``) with
+    ``attn_type="hept"``: same constructor ``(attn_type, coords_dim, **kwargs)``, same ``forward(x, kwargs)`` with the
+    kwargs of ``prepare_input_src``, same state-dict names and shapes (``attn.e2lsh.beta`` included), so the
+    ``attns.{i}.*`` entries of a src checkpoint load with ``strict=True``.  Positional encodings (``pe_type``
+    "learned" / "fixed") are not supported; "none" or no ``pe_type`` is the reference's ``pe_func = None``."""
+
+    def __init__(self, attn_type, coords_dim, *, precision: str = "fp32", **kwargs):
+        if attn_type != "hept":   # (the reference raises NotImplementedError for a type it does not know)
+            raise NotImplementedError(f"hept_amd.SrcAttn implements attn_type='hept' only, got {attn_type!r}")
+        pe_type = kwargs.get("pe_type")
+        if pe_type in ("learned", "fixed"):
+            raise NotImplementedError(f"hept_amd.SrcAttn: pe_type={pe_type!r} is not supported (positional encodings "
+                                      "are not implemented); use pe_type='none'")
+        if kwargs.pop("variant", "src") != "src":
+            raise ValueError("hept_amd.SrcAttn wraps the src variant of the operator only")
+        super().__init__(coords_dim, precision=precision, variant="src", **kwargs)
+        self.attn_type = attn_type
+        self.pe_func = None    # get_pe_func(pe_type) for any type but "learned" / "fixed"

@@ -157,23 +157,31 @@ class HeptPartialSumsFused(torch.autograd.Function):
     Backward: the HIP backward of the block attention yields dq, dk, dv; the small dense part behind them (three
     (N, 192) x (192, 24) products for d LayerNorm(x), three transposed ones for the weight gradients, the LayerNorm
     backward) is plain torch on the saved ``x`` -- the normalised rows are recomputed, nothing of size (N, 192) is kept
-    between the passes."""
+    between the passes.
+
+    ``geo`` = (eta, phi, cfac, raw_size) selects the src variant's block (``codes`` is then None), as in
+    :class:`HeptPartialSums`: rows at and after ``raw_size`` are zero in q^, k^, v, so dq, dk, dv vanish there and the
+    LayerNorm and projection backward sees the reference's in-place zero fill."""
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, eps, w_q, w_k, w_v, coords, sqrt_w, alpha, codes, block_size, f32_mfma=False,
-                tiles="fp32"):
+                tiles="fp32", geo=None):
         from ._lib import MAX_TABLES
 
         n, d = x.shape
         n_tables = alpha.shape[2]
+        raw = n if geo is None else int(geo[3])
         qs, ks = [], []
         rows = None   # see HeptPartialSums.forward
         for c0 in range(0, n_tables, MAX_TABLES):
             tc = min(MAX_TABLES, n_tables - c0)
             ph = ops.prep_hash_fused(x, ln_w, ln_b, eps, w_q, w_k, w_v, coords, sqrt_w, alpha, codes, tiles, t0=c0, tl=tc,
-                                     rows=rows)
+                                     raw_size=raw, rows=rows)
             rows = (ph["qhat"], ph["kvhat"])
-            qp, kp = ops.sort_tables(ph["qproj"], ph["kproj"], codes, ph["minmax"], t0=c0)
+            if geo is None:
+                qp, kp = ops.sort_tables(ph["qproj"], ph["kproj"], codes, ph["minmax"], t0=c0)
+            else:
+                qp, kp = ops.sort_tables_src(ph["qproj"], ph["kproj"], geo[0], geo[1], geo[2], ph["minmax"], t0=c0)
             qs.append(qp)
             ks.append(kp)
         qpos, kpos = (qs[0], ks[0]) if len(qs) == 1 else (torch.cat(qs), torch.cat(ks))
@@ -182,6 +190,7 @@ class HeptPartialSumsFused(torch.autograd.Function):
         ctx.f32_mfma = f32_mfma
         ctx.save_for_backward(ph["qhat"], ph["kvhat"], qpos, kpos, coords, sqrt_w, x, ln_w, ln_b, w_q, w_k, w_v)
         ctx.dims = (d, coords.shape[1], block_size, float(eps))
+        ctx.raw_size = raw
         return acc
 
     @staticmethod
@@ -189,7 +198,7 @@ class HeptPartialSumsFused(torch.autograd.Function):
         qhat, kvhat, qpos, kpos, coords, sqrt_w, x, ln_w, ln_b, w_q, w_k, w_v = ctx.saved_tensors
         d, c, block_size, eps = ctx.dims
         dq, dk, dv, dcs, dsw = ops.block_attn_bwd(qhat, kvhat, qpos, kpos, gacc.contiguous(), d, c, block_size,
-                                                  f32_mfma=ctx.f32_mfma, coords=coords, raw_size=x.shape[0])
+                                                  f32_mfma=ctx.f32_mfma, coords=coords, raw_size=ctx.raw_size)
         need = ctx.needs_input_grad
         dx = dlw = dlb = dwq = dwk = dwv = None
         if any(need[i] for i in (0, 1, 2, 4, 5, 6)):   # (a frozen front end: nothing behind dq, dk, dv is computed)
@@ -203,7 +212,7 @@ class HeptPartialSumsFused(torch.autograd.Function):
         dcoords = (dcs * sqrt_w[None]).sum(dim=1) if need[7] else None
         return (dx if need[0] else None, dlw if need[1] else None, dlb if need[2] else None, None,
                 dwq if need[4] else None, dwk if need[5] else None, dwv if need[6] else None, dcoords,
-                dsw if need[8] else None, None, None, None, None, None)
+                dsw if need[8] else None, None, None, None, None, None, None)
 
 
 class HeptCombine(torch.autograd.Function):

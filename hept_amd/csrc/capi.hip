@@ -189,7 +189,7 @@ void hept_prof_mark_sort_mid(void* stream) {
     if (g_prof.mode == 2 && prof_active() && !g_prof.mid[g_prof.n_calls]) prof_mark(PROF_SORT_MID, (hipStream_t)stream);
 }
 
-extern "C" int hept_abi_version(void) { return 20; }
+extern "C" int hept_abi_version(void) { return 21; }
 
 extern "C" int hept_part_precision(int precision, int D) {
     return (precision != HEPT_PREC_F32 && precision != HEPT_PREC_F32_MFMA && precision != HEPT_PREC_F32_DIFF && D == 24) ? HEPT_PREC_BF16 : HEPT_PREC_F32;
@@ -627,11 +627,14 @@ extern "C" int hept_forward_sharded_src(hept_comm* comm, const float* q, const f
                                 transport, workspace, workspace_bytes, xbuf, xbuf_bytes, out_full, stream);
 }
 
-extern "C" int hept_attn_block_forward(const float* x, const float* coords, const int64_t* codes,
-                                       const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B,
-                                       int precision, void* workspace, size_t workspace_bytes, float* y,
-                                       void* stream) {
-    if (!x || !coords || !codes || !p || !workspace || !y) return HEPT_ERR_ARG;
+namespace {
+// the whole Attn block for either variant: geo.eta == nullptr takes the example variant's AND codes, else the src
+// variant's region shift and padding rows (rows >= geo.raw_size: zero q^, k^, v, hash +inf; the residual and the
+// feed-forward still run on them, as in the reference's block)
+int attn_block_impl(const float* x, const float* coords, const int64_t* codes, const GeoShift& geo,
+                    const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B, int precision,
+                    void* workspace, size_t workspace_bytes, float* y, void* stream) {
+    if (!x || !coords || !p || !workspace || !y) return HEPT_ERR_ARG;
     if (!p->norm1_w || !p->norm1_b || !p->w_q || !p->w_k || !p->w_v || !p->w_rpe || !p->alpha || !p->out_w ||
         !p->norm2_w || !p->norm2_b || !p->ff1_w || !p->ff1_b || !p->ff2_w || !p->ff2_b)
         return HEPT_ERR_ARG;
@@ -642,6 +645,7 @@ extern "C" int hept_attn_block_forward(const float* x, const float* coords, cons
     if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     prof_mark(0, st);
+    const int raw_size = geo.eta ? geo.raw_size : N;
     int32_t* qpos = w.pos;
     int32_t* kpos = w.pos + (size_t)T * H * N;
     // any number of tables: the row builder and the sort walk chunks of HEPT_MAX_TABLES, as run_begin does (the rows
@@ -653,14 +657,17 @@ extern "C" int hept_attn_block_forward(const float* x, const float* coords, cons
         size_t zbytes = 0;
         hept_sort_zero_block(w.sort_ws, N, H, tc, &zptr, &zbytes);   // (see run_begin)
         rc = hept_prep_hash_fused_rpe(x, p->norm1_w, p->norm1_b, p->eps1, p->w_q, p->w_k, p->w_v, coords, p->w_rpe, K,
-                                      p->alpha, codes, N, N, H, D, C, T, c0, tc, precision, w.qhat, w.kvhat, w.qproj,
+                                      p->alpha, codes, N, raw_size, H, D, C, T, c0, tc, precision, w.qhat, w.kvhat, w.qproj,
                                       w.kproj, w.minmax, stream, zptr, zbytes);
         if (rc) return rc;
         if (c0 == 0) prof_mark(1, st);
         int32_t* cq = T <= HEPT_MAX_TABLES ? qpos : w.pos_chunk;
         int32_t* ck = cq + (size_t)tc * H * N;
-        rc = hept_sort_tables_rows(w.qproj, w.kproj, codes, w.minmax, N, H, T, c0, tc, w.sort_ws, cq, ck, nullptr, stream,
-                                   zbytes != 0);
+        // (no rows job: the fused row builder writes the v half itself)
+        rc = geo.eta ? hept_sort_tables_src_rows(w.qproj, w.kproj, geo.eta, geo.phi, geo.cfac, w.minmax, N, H, T, c0, tc,
+                                                 w.sort_ws, cq, ck, nullptr, stream, zbytes != 0)
+                     : hept_sort_tables_rows(w.qproj, w.kproj, codes, w.minmax, N, H, T, c0, tc, w.sort_ws, cq, ck, nullptr,
+                                             stream, zbytes != 0);
         if (rc) return rc;
         if (cq != qpos) {
             const size_t off = (size_t)c0 * H * N, bytes = (size_t)tc * H * N * 4;
@@ -678,6 +685,27 @@ extern "C" int hept_attn_block_forward(const float* x, const float* coords, cons
     prof_mark(4, st);
     prof_call_done();
     return rc;
+}
+}  // namespace
+
+extern "C" int hept_attn_block_forward(const float* x, const float* coords, const int64_t* codes,
+                                       const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B,
+                                       int precision, void* workspace, size_t workspace_bytes, float* y,
+                                       void* stream) {
+    if (!codes) return HEPT_ERR_ARG;
+    return attn_block_impl(x, coords, codes, GeoShift{}, p, N, H, D, C, K, T, B, precision, workspace, workspace_bytes,
+                           y, stream);
+}
+
+extern "C" int hept_attn_block_forward_src(const float* x, const float* coords, const float* eta_idx,
+                                           const float* phi_idx, const float* cfac, int raw_size,
+                                           const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B,
+                                           int precision, void* workspace, size_t workspace_bytes, float* y,
+                                           void* stream) {
+    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
+    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
+    return attn_block_impl(x, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, p, N, H, D, C, K, T, B,
+                           precision, workspace, workspace_bytes, y, stream);
 }
 
 extern "C" int hept_profile_enable(int mode, int max_calls) {

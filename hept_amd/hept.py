@@ -247,22 +247,30 @@ class HEPTAttention(nn.Module):
 
     def _train_fused_ok(self, x, kwargs) -> bool:
         """Whether the training-mode ``Attn`` block may hand its LayerNorm and projections to the fused row builder"""
+        keys = ("raw_size", "region_indices", "regions_h") if self.variant == "src" else ("combined_shifts",)
         return (x.is_cuda and self.dim_per_head == 24 and self.num_heads == 8 and self.sharding is None
-                and "combined_shifts" in kwargs and kwargs["coords"].shape[1] in (2, 4, 6)
+                and all(k in kwargs for k in keys) and kwargs["coords"].shape[1] in (2, 4, 6)
                 and x.dim() == 2 and x.shape[0] % self.block_size == 0)
 
     def _forward_train_fused(self, x, norm1, w_q, w_k, w_v, **kwargs):
         """Training mode of the ``Attn`` block (``hept_amd.Attn``): LayerNorm + the three projections + the operator as
         one autograd node whose forward never materialises q, k, v (``autograd.HeptPartialSumsFused``); returns the
-        operator's output (N, D), reference ``example/transformer.py:155-159``."""
+        operator's output (N, D), reference ``example/transformer.py:155-159`` (``variant="src"``: the src block's
+        kwargs, ``src/models/baselines/transformer.py:208-211``)."""
         from .autograd import HeptCombine, HeptPartialSumsFused, RpeScale
 
         h, d = self.num_heads, self.dim_per_head
         sqrt_w = RpeScale.apply(kwargs["w_rpe"].weight.float(), h, d, self.num_w_per_dist)
+        codes, geo = None, None
+        if self.variant == "src":
+            geo = ops.geo_args(kwargs["region_indices"], kwargs["regions_h"], self.n_hashes, h, x.shape[0]) + (
+                int(kwargs["raw_size"]),)
+        else:
+            codes = kwargs["combined_shifts"]
         acc = HeptPartialSumsFused.apply(x.float(), norm1.weight.float(), norm1.bias.float(), norm1.eps, w_q.weight.float(),
                                          w_k.weight.float(), w_v.weight.float(), kwargs["coords"].float(), sqrt_w,
-                                         self.e2lsh.alpha.detach(), kwargs["combined_shifts"], self.block_size,
-                                         self.precision == "fp32_mfma", self._train_tiles())
+                                         self.e2lsh.alpha.detach(), codes, self.block_size,
+                                         self.precision == "fp32_mfma", self._train_tiles(), geo)
         return HeptCombine.apply(acc, self.out_linear.weight, self.out_linear.bias).to(x.dtype)
 
     def _forward_train(self, query, key, value, **kwargs):

@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 
-__all__ = ["forward_op", "forward_src_op", "attn_block_op"]
+__all__ = ["forward_op", "forward_src_op", "attn_block_op", "attn_block_src_op"]
 
 
 @torch.library.custom_op("hept_amd::forward", mutates_args=(), device_types="cuda")
@@ -68,4 +68,26 @@ def attn_block_op(x: torch.Tensor, coords: torch.Tensor, codes: torch.Tensor, no
 @attn_block_op.register_fake
 def _(x, coords, codes, norm1_w, norm1_b, w_q, w_k, w_v, w_rpe, alpha, out_w, out_b, norm2_w, norm2_b, ff1_w, ff1_b,
       ff2_w, ff2_b, num_heads, block_size, w_per_dist, eps1, eps2, precision):
+    return x.new_empty(x.shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("hept_amd::attn_block_src", mutates_args=(), device_types="cuda")
+def attn_block_src_op(x: torch.Tensor, coords: torch.Tensor, eta_idx: torch.Tensor, phi_idx: torch.Tensor,
+                      regions_h: torch.Tensor, raw_size: int, norm1_w: torch.Tensor, norm1_b: torch.Tensor,
+                      w_q: torch.Tensor, w_k: torch.Tensor, w_v: torch.Tensor, w_rpe: torch.Tensor, alpha: torch.Tensor,
+                      out_w: torch.Tensor, out_b: torch.Tensor, norm2_w: torch.Tensor, norm2_b: torch.Tensor,
+                      ff1_w: torch.Tensor, ff1_b: torch.Tensor, ff2_w: torch.Tensor, ff2_b: torch.Tensor, num_heads: int,
+                      block_size: int, w_per_dist: int, eps1: float, eps2: float, precision: str) -> torch.Tensor:
+    """The src variant's Attn block (reference ``src/models/baselines/transformer.py:205-214``, eval mode) as one
+    graph node."""
+    params = dict(zip(_ATTN_KEYS, (norm1_w, norm1_b, w_q, w_k, w_v, w_rpe, alpha, out_w, out_b, norm2_w, norm2_b,
+                                   ff1_w, ff1_b, ff2_w, ff2_b)))
+    return ops.attn_block_forward_src(x, coords, (eta_idx, phi_idx), regions_h, raw_size, params, num_heads=num_heads,
+                                      block_size=block_size, w_per_dist=w_per_dist, eps1=eps1, eps2=eps2,
+                                      precision=precision)
+
+
+@attn_block_src_op.register_fake
+def _(x, coords, eta_idx, phi_idx, regions_h, raw_size, norm1_w, norm1_b, w_q, w_k, w_v, w_rpe, alpha, out_w, out_b,
+      norm2_w, norm2_b, ff1_w, ff1_b, ff2_w, ff2_b, num_heads, block_size, w_per_dist, eps1, eps2, precision):
     return x.new_empty(x.shape, dtype=torch.float32)

@@ -18,7 +18,7 @@ __all__ = [
     "precision_code", "rpe_scale", "prep_hash", "sort_tables", "block_attn", "reduce_tables", "combine_out",
     "forward", "forward_partial", "workspace_bytes", "profile_enable", "profile_read", "unpack_part",
     "segmented_argsort", "block_attn_bwd", "sort_tables_src", "forward_src", "forward_partial_src", "geo_args",
-    "packed_partials", "prep_hash_fused", "combine_ffn", "attn_block_forward", "combine_bwd", "rpe_scale_bwd",
+    "packed_partials", "prep_hash_fused", "combine_ffn", "attn_block_forward", "attn_block_forward_src", "combine_bwd", "rpe_scale_bwd",
     "partial_begin", "partial_heads", "combine_groups", "forward_sharded", "rows_wgrad", "ln_bwd", "ln_ffn_fwd",
     "ln_ffn_bwd",
 ]
@@ -577,29 +577,26 @@ def combine_ffn(part: torch.Tensor, head_dim: int, out_weight, out_bias, x, norm
     return y
 
 
-@_on_device
-def attn_block_forward(x, coords, codes, params: Dict[str, torch.Tensor], *, num_heads: int, block_size: int,
-                       w_per_dist: int, eps1: float = 1e-5, eps2: float = 1e-5, precision="fp32",
-                       workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The whole Attn block (reference ``example/transformer.py:154-165``, eval mode) in one C call.
-    ``params`` holds the block's tensors under the reference's state-dict names."""
+_BLOCK_NAMES = {"norm1_w": "norm1.weight", "norm1_b": "norm1.bias", "w_q": "w_q.weight", "w_k": "w_k.weight",
+                "w_v": "w_v.weight", "w_rpe": "w_rpe.weight", "alpha": "attn.e2lsh.alpha",
+                "out_w": "attn.out_linear.weight", "out_b": "attn.out_linear.bias", "norm2_w": "norm2.weight",
+                "norm2_b": "norm2.bias", "ff1_w": "ff.0.weight", "ff1_b": "ff.0.bias", "ff2_w": "ff.2.weight",
+                "ff2_b": "ff.2.bias"}
+
+
+def _block_args(x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace):
+    """Checks and marshalling shared by the two one-call blocks: (x, coords, params struct, sizes, prec, workspace,
+    the tensors the struct points into)."""
     lib = _lib.load()
-    names = {"norm1_w": "norm1.weight", "norm1_b": "norm1.bias", "w_q": "w_q.weight", "w_k": "w_k.weight",
-             "w_v": "w_v.weight", "w_rpe": "w_rpe.weight", "alpha": "attn.e2lsh.alpha",
-             "out_w": "attn.out_linear.weight", "out_b": "attn.out_linear.bias", "norm2_w": "norm2.weight",
-             "norm2_b": "norm2.bias", "ff1_w": "ff.0.weight", "ff1_b": "ff.0.bias", "ff2_w": "ff.2.weight",
-             "ff2_b": "ff.2.bias"}
     x = _f32c(x, "x")
     coords = _f32c(coords, "coords")
-    keep = {f: _f32c(params[k], k) for f, k in names.items()}
+    keep = {f: _f32c(params[k], k) for f, k in _BLOCK_NAMES.items()}
     n, d = x.shape
     h = num_heads
     e, t = keep["alpha"].shape[1], keep["alpha"].shape[2]
     c = e - d
     if n % block_size != 0:
         raise ValueError(f"number of points {n} is not a multiple of block_size {block_size}")
-    if codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n):
-        raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}")
     # the row builder indexes these by the sizes above: a mismatched tensor would be an out-of-bounds device read
     if keep["alpha"].shape[0] != h or tuple(coords.shape) != (n, c):
         raise ValueError(f"attn.e2lsh.alpha must be ({h}, D + C, n_hashes) and coords ({n}, {c})")
@@ -608,20 +605,57 @@ def attn_block_forward(x, coords, codes, params: Dict[str, torch.Tensor], *, num
         raise ValueError(f"w_rpe.weight must have shape {want_rpe}, got {tuple(keep['w_rpe'].shape)}")
     for f_ in ("w_q", "w_k", "w_v"):
         if tuple(keep[f_].shape) != (h * d, d):
-            raise ValueError(f"{names[f_]} must have shape {(h * d, d)}")
-    codes = codes.contiguous()
+            raise ValueError(f"{_BLOCK_NAMES[f_]} must have shape {(h * d, d)}")
     prec = precision_code(precision)
     _lib.check(lib.hept_check_shape(n, h, d, c, t, block_size), "hept_check_shape")
     need = int(lib.hept_workspace_bytes(n, h, d, c, t, block_size, prec))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
     st = _lib.AttnParams(**{f: v.data_ptr() for f, v in keep.items()}, eps1=float(eps1), eps2=float(eps2))
+    return x, coords, st, (n, h, d, c, t), prec, workspace, keep
+
+
+@_on_device
+def attn_block_forward(x, coords, codes, params: Dict[str, torch.Tensor], *, num_heads: int, block_size: int,
+                       w_per_dist: int, eps1: float = 1e-5, eps2: float = 1e-5, precision="fp32",
+                       workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The whole Attn block (reference ``example/transformer.py:154-165``, eval mode) in one C call.
+    ``params`` holds the block's tensors under the reference's state-dict names."""
+    lib = _lib.load()
+    x, coords, st, (n, h, d, c, t), prec, workspace, _keep = _block_args(
+        x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace)
+    if codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n):
+        raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}")
+    codes = codes.contiguous()
     y = torch.empty(n, d, device=x.device, dtype=torch.float32)
     import ctypes
 
     _lib.check(lib.hept_attn_block_forward(x.data_ptr(), coords.data_ptr(), codes.data_ptr(), ctypes.byref(st), n, h,
                                            d, c, w_per_dist, t, block_size, prec, workspace.data_ptr(),
                                            workspace.numel(), y.data_ptr(), _stream(x)), "hept_attn_block_forward")
+    return y
+
+
+@_on_device
+def attn_block_forward_src(x, coords, region_indices, regions_h, raw_size: int, params: Dict[str, torch.Tensor], *,
+                           num_heads: int, block_size: int, w_per_dist: int, eps1: float = 1e-5, eps2: float = 1e-5,
+                           precision="fp32", workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The src variant's Attn block (reference ``src/models/baselines/transformer.py:205-214`` with
+    ``attn_type="hept"``, eval mode) in one C call; the operator's kwargs as built by ``prepare_input_src``."""
+    lib = _lib.load()
+    x, coords, st, (n, h, d, c, t), prec, workspace, _keep = _block_args(
+        x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace)
+    eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
+    raw_size = int(raw_size)
+    if not 0 <= raw_size <= n:
+        raise ValueError(f"raw_size must lie in [0, {n}], got {raw_size}")
+    y = torch.empty(n, d, device=x.device, dtype=torch.float32)
+    import ctypes
+
+    _lib.check(lib.hept_attn_block_forward_src(x.data_ptr(), coords.data_ptr(), eta.data_ptr(), phi.data_ptr(),
+                                               cfac.data_ptr(), raw_size, ctypes.byref(st), n, h, d, c, w_per_dist, t,
+                                               block_size, prec, workspace.data_ptr(), workspace.numel(), y.data_ptr(),
+                                               _stream(x)), "hept_attn_block_forward_src")
     return y
 
 

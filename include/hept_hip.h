@@ -343,6 +343,14 @@ int hept_combine_ffn(const float* part, int part_precision, int Tl, int N, int H
 int hept_attn_block_forward(const float* x, const float* coords, const int64_t* codes,
                             const hept_attn_params* params, int N, int H, int D, int C, int K, int T, int B,
                             int precision, void* workspace, size_t workspace_bytes, float* y, void* stream);
+/* The same block around the src variant's operator (src/models/baselines/transformer.py:160-229 with
+ * src/models/attention/hept.py): eta_idx / phi_idx / cfac / raw_size as for hept_forward_src, no AND codes.  Rows
+ * >= raw_size are padding inside the operator (zero q^, k^, v; hash +inf) but still get the residual, norm2 and the
+ * feed-forward, as in the reference.  Workspace: hept_workspace_bytes(N, H, D, C, T, B, precision). */
+int hept_attn_block_forward_src(const float* x, const float* coords, const float* eta_idx, const float* phi_idx,
+                                const float* cfac, int raw_size, const hept_attn_params* params, int N, int H,
+                                int D, int C, int K, int T, int B, int precision, void* workspace,
+                                size_t workspace_bytes, float* y, void* stream);
 
 /* SURVEY.md §8 f-2 — backward of the block attention (the reference trains through example/hept.py:55-80 with
  * plain autograd; there is no custom backward to mirror).  f32 tiles only; the tile products run as split-bf16
