@@ -14,10 +14,13 @@ process starts N children (one per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in t
 *before it makes any GPU call*, never touches the GPU itself, relays rank 0's JSON line and exits
 non-zero if any child failed.  Under ``torch.distributed.run`` (WORLD_SIZE set) it is a rank.
 
-Beside the headline the line carries: ``fp32`` (N = 1: the reference-precision run of the same
-workload, measured in the same process before the headline region), ``c4`` (BASELINE config 4: one table
-per GPU, n_hashes = N), ``roofline`` (HBM bound, dominant kernel, HIP events on the launch stream)
-and ``cpu_baseline`` (N = 1).  See DESIGN.md §6 for every field.
+A plain run does only what the headline needs: set up, warm up, time the K steps, write ``--dump-outputs``, print
+the line -- the contract's fields, ``config``, the headline ``roofline`` (HBM bound, dominant kernel, read off the HIP
+events of the timed region itself) and a ``summary``.  ``--full`` adds every other record, each measured as before:
+``fp32`` and ``mixed16`` (N = 1: the other tile precisions of the same workload, measured in the same process before
+the headline region), the other BASELINE configurations, ``c4`` (BASELINE config 4: one table per GPU, n_hashes = N),
+``kernels`` / ``step_roofline`` (an extra pass with every stage bracketed), the exchange's per-term times and
+``cpu_baseline`` (N = 1).  See DESIGN.md §6 for every field.
 """
 from __future__ import annotations
 
@@ -42,6 +45,10 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec ...
 HBM_COPY_GBS = 6290.0      # ... and the 6.29 TB/s the same guide measures for a device copy (roofline.frac_of_copy)
 MFMA_BF16_PEAK_TF = 2500.0  # dense bf16 MFMA (both the bf16 and the split-bf16 f32 kernel issue bf16 MFMAs)
 B, H, D = 128, 8, 24
+# a plain run keeps the device busy with the headline's step this long before the region, in place of the sub-records
+# that precede it in a --full run: without it a 20-step region reads 175 us per step instead of 157; 0.1 s (about what
+# config 4's record ran right before the region) fell short on one box of four, 0.5 s matched the --full headline on each
+PLAIN_BUSY_S = 0.5
 
 
 def parse_args(argv=None):
@@ -53,8 +60,11 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--tables-per-gpu", type=int, default=TABLES_PER_GPU,
                     help="hash tables per GPU (default 3 = BASELINE config 3 at N=1; 1 = config 4: n_hashes = #GPUs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the fp32 and c4 sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every record beside the headline: other precisions and configurations, per-kernel "
+                         "and whole-step rooflines, the exchange's terms, the CPU baseline (default: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the precision and configuration sub-records")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N>1 code path (process group, exchange step, barriers) even with one rank: a self-check")
     ap.add_argument("--stages", action="store_true", help="also print a per-stage HIP-event breakdown to stderr")
@@ -436,14 +446,18 @@ def worker(args) -> int:
             keep["out"] = out.detach().float().cpu()
         return elapsed, stage_ms["block_attn"] / max(n_rec, 1) * launches, n_rec
 
+    def keep_busy(step, seconds):
+        """Issue steps for ``seconds`` of host time (untimed, unsampled): a device that idled comes up to its clocks"""
+        t_busy = time.perf_counter()
+        while time.perf_counter() - t_busy < seconds:
+            step()
+
     def measure_median(step, steps, warmup, regions=3):
         """A sub-record's region on a device that has just idled through a module build (tens of ms of host work) can
         fall inside its clock ramp, and one scheduling hiccup of a shared host doubles a 50 ms region (one refresh of round 6
         read 431 us per forward for the fp32 record, 264-275 us in every other run): keep the device busy for 30 ms, then
         take the median of three regions -- as the per-configuration records do."""
-        t_busy = time.perf_counter()
-        while time.perf_counter() - t_busy < 0.03:
-            step()
+        keep_busy(step, 0.03)
         runs = sorted((measure(step, steps, warmup) for _ in range(regions)), key=lambda r: r[0])
         return runs[len(runs) // 2]
 
@@ -523,11 +537,11 @@ def worker(args) -> int:
                 "step_roofline": {"bound": "hbm", "algorithmic_bytes": total, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                   "frac": gbs / HBM_PEAK_GBS, "frac_of_copy": gbs / HBM_COPY_GBS}}
 
-    def exchange_record(attn, step, steps=30):
+    def exchange_record(attn, step, steps=30, terms=True):
         """What ran between the GPUs, said by the objects that ran it: the transport and head groups after the ladder
         and tuning, the world size of the communicator that moved the rows (hept_comm_world -- not torch's process
-        group), and per-term HIP-event times of the sharded step (one extra, untimed pass with every stage bracketed:
-        exposed push / transfer of the last head group, combine, output gather)."""
+        group), and (``terms``) per-term HIP-event times of the sharded step (one extra, untimed pass with every stage
+        bracketed: exposed push / transfer of the last head group, combine, output gather)."""
         sh = attn.sharding
         rec = {"describe": sh.describe(), "head_groups": launches_per_step(attn), "comm_world": 0, "transport": "torch.distributed"}
         if sh._native:
@@ -535,6 +549,7 @@ def worker(args) -> int:
 
             rec["comm_world"] = int(_lib.load().hept_comm_world(sh._native))
             rec["transport"] = "rccl" if (sh._p2p_failed or sh.exchange == "rccl") else "one-sided"
+        if sh._native and terms:
             ops.profile_enable(2, steps + 2)
             fence()
             for _ in range(steps):
@@ -738,12 +753,17 @@ def worker(args) -> int:
                 del attn4, step4
         return sub
 
-    # One process: the sub-records run BEFORE the headline region -- they are part of every default run anyway, and
-    # after them the device is in its steady state (clocks up, code objects and workspaces resident), which W = 5
-    # steps (1 ms) alone do not reach on a GPU that idled while the process started (tools/event_cost.py, DESIGN.md
-    # section 6).  Several ranks: settle() has already run hundreds of steps, and the headline module's exchange
-    # buffers are released before config 4 builds its own.
-    sub = sub_records() if not multi else {}
+    # One process, --full: the sub-records run BEFORE the headline region, and after them the device is in its steady
+    # state (clocks up, code objects and workspaces resident), which W = 5 steps (1 ms) alone do not reach on a GPU that
+    # idled while the process started (tools/event_cost.py).  A plain run brings the device to that
+    # state with the headline's own step instead (PLAIN_BUSY_S).  Several ranks: settle() has already run hundreds of
+    # steps, and the headline module's exchange buffers are released before config 4 builds its own.
+    sub = {}
+    if not multi:
+        if args.full:
+            sub = sub_records()
+        else:
+            keep_busy(step, PLAIN_BUSY_S)
 
     # ---------------------------------------------------------------------------------------------- headline region
     dumped = {} if args.dump_outputs else None
@@ -752,7 +772,7 @@ def worker(args) -> int:
     exch = None
     if multi:
         attn.sharding.check()   # a one-sided wait that timed out inside the region voids the measurement
-        exch = exchange_record(attn, step)
+        exch = exchange_record(attn, step, terms=args.full)
         exch.update(head_tune)
         attn.sharding.check()
 
@@ -789,12 +809,12 @@ def worker(args) -> int:
         }
         if exch:
             line["exchange"] = exch
-    if not multi:
+    if not multi and args.full:
         ws = whole_step(step, n, C, tables_per_gpu, args.precision, ms_per_step)
         if rank == 0:
             line.update(ws)
     del attn, step
-    if multi:
+    if multi and args.full:
         sub = sub_records()
     if rank == 0:
         line.update(sub)
@@ -802,7 +822,7 @@ def worker(args) -> int:
     if rank == 0 and world == 1 and not multi and not args.no_extra and "c4" in line:
         line["c4"]["exchange_on_one_rank_us"] = exchange_proxy(args.precision)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(inp, B)
         # The driver keeps the last 8 KB of stdout: the long per-configuration sub-records go to the FRONT of the line, the
         # contract's fields, the headline roofline, the CPU baseline, the reference-precision record and the per-launch

@@ -48,12 +48,38 @@ def _check_whole_step(rec, n_launches):
     assert 0.7 < sum(k["ms"] for k in ks) / rec["ms_per_step"] < 1.3
 
 
+def _check_headline(d, precision, dtype):
+    """The contract's fields and the headline roofline (read off the timed region's own HIP events): in every line"""
+    assert d["config"]["rccl_ranks"] == 0
+    assert KEYS <= set(d) and ROOF <= set(d["roofline"])
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["metric"] == "attention-fwd points/sec" and d["unit"] == "points/s" and d["scaling"] == "weak"
+    assert d["dtype"].startswith(dtype) and d["data"] == "synthetic" and d["vs_baseline"] is None
+    assert "tracking-60k" in d["config"]["workload"] and "model" not in d["config"]
+    r = d["roofline"]
+    assert r["bound"] in ("hbm", "mfma") and 0.0 < r["frac"] < 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
+    assert abs(r["frac_of_copy"] - r["achieved"] / 6290.0) < 1e-9
+    # PMC traffic is copied from profiles/ only when the record belongs to this build and this kernel template
+    src = r["traffic_source"]
+    assert src["kernel_launched"].startswith("block_attn_split_kernel<4" if precision == "fp32" else "block_attn_kernel<4")
+    if r["traffic"] is None:
+        # refused for a reason that is not this test's business (a stale digest on a tree under development) -- but never
+        # because bench.py and the library disagree about the NAME of the kernel that ran (round 6 shipped that twice)
+        assert "refused" in src and "no PMC pass" not in src["refused"], src
+    else:
+        assert "refused" not in src and src["kernel_launched"] in src["kernel_measured"].replace(" ", "")
+        assert src["workload_key"] == f"c3/{precision}"
+        _check_traffic(r)
+    assert 0.0 < r["frac"] <= r["frac_adjusted"] < 1.0 and "HIP events" in r["timing_method"]
+    assert 1e7 < d["value"] < 1e10 and abs(d["value"] - 60000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+
+
 @pytest.mark.parametrize("precision,dtype", [("bf16", "bf16"), ("fp32", "f32")])
 def test_bench_line(precision, dtype, gpu_device):
-    d = _run("--precision", precision, "--no-cpu-baseline")
+    d = _run("--full", "--precision", precision, "--no-cpu-baseline")
     _check_whole_step(d, 5)
     assert [k["name"].split()[0] for k in d["kernels"]][1:3] == ["chunk_sort_kernel", "bucket_sort_kernel"]
-    if precision == "bf16":  # the default run carries the reference-precision record and BASELINE config 4
+    if precision == "bf16":  # the --full run carries the reference-precision record and BASELINE config 4
         f = d["fp32"]
         assert f["dtype"].startswith("f32 rows") and "split-bf16" in f["dtype"]
         assert f["ms_per_step"] > d["ms_per_step"] and 0.0 < f["roofline"]["frac"] < 1.0
@@ -81,27 +107,7 @@ def test_bench_line(precision, dtype, gpu_device):
                     _check_traffic(roof)
         # the batched call runs ten 6k clouds at the per-point rate of one 60k cloud, not of one 6k cloud
         assert d["c2x10"]["bf16"]["value"] > 2.0 * d["c2"]["bf16"]["value"]
-    assert d["config"]["rccl_ranks"] == 0
-    assert KEYS <= set(d) and ROOF <= set(d["roofline"])
-    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 2 and d["higher_is_better"] is True
-    assert d["metric"] == "attention-fwd points/sec" and d["unit"] == "points/s" and d["scaling"] == "weak"
-    assert d["dtype"].startswith(dtype) and d["data"] == "synthetic" and d["vs_baseline"] is None
-    assert "tracking-60k" in d["config"]["workload"] and "model" not in d["config"]
-    r = d["roofline"]
-    assert r["bound"] in ("hbm", "mfma") and 0.0 < r["frac"] < 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
-    assert abs(r["frac_of_copy"] - r["achieved"] / 6290.0) < 1e-9
-    # PMC traffic is copied from profiles/ only when the record belongs to this build and this kernel template
-    src = r["traffic_source"]
-    assert src["kernel_launched"].startswith("block_attn_split_kernel<4" if precision == "fp32" else "block_attn_kernel<4")
-    if r["traffic"] is None:
-        # refused for a reason that is not this test's business (a stale digest on a tree under development) -- but never
-        # because bench.py and the library disagree about the NAME of the kernel that ran (round 6 shipped that twice)
-        assert "refused" in src and "no PMC pass" not in src["refused"], src
-    else:
-        assert "refused" not in src and src["kernel_launched"] in src["kernel_measured"].replace(" ", "")
-        assert src["workload_key"] == f"c3/{precision}"
-        _check_traffic(r)
-    assert 0.0 < r["frac"] <= r["frac_adjusted"] < 1.0 and "HIP events" in r["timing_method"]
+    _check_headline(d, precision, dtype)
     # the driver keeps the last 8 KB of stdout: the reference-precision record, the per-launch list and the summary close
     # the line, the long per-configuration records open it
     keys = list(d)
@@ -112,7 +118,19 @@ def test_bench_line(precision, dtype, gpu_device):
         assert d["summary"]["fp32_ms_per_step"] == d["fp32"]["ms_per_step"]
         tail = json.dumps(d)[-8192:]
         assert '"fp32": {"ms_per_step"' in tail and '"step_roofline"' in tail and '"kernels"' in tail
-    assert 1e7 < d["value"] < 1e10 and abs(d["value"] - 60000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+
+
+@pytest.mark.parametrize("precision,dtype", [("bf16", "bf16"), ("fp32", "f32")])
+def test_plain_bench_line_is_the_headline_alone(precision, dtype, gpu_device):
+    """Without --full the line carries the contract's fields, the headline roofline and the summary, and nothing that
+    takes runs of its own: no other precision or configuration, no per-launch list, no CPU baseline."""
+    d = _run("--precision", precision)
+    _check_headline(d, precision, dtype)
+    assert list(d) == ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                       "vs_baseline", "dtype", "data", "config", "roofline", "summary"]
+    assert d["config"]["comm_world"] == 0 and d["config"]["transport"] is None
+    assert set(d["summary"]) == {"ms_per_step", "points_per_s", "block_attn_ms", "roofline_frac", "traffic", "mfma_busy_frac"}
+    assert d["summary"]["ms_per_step"] == d["ms_per_step"] and d["summary"]["points_per_s"] == d["value"]
 
 
 def test_bench_dumps_the_output_of_its_last_timed_step(tmp_path, gpu_device):
@@ -149,7 +167,7 @@ def test_bench_launches_its_own_ranks(ranks, gpu_device):
     # (HEPT_EXCHANGE=torch: the collectives go through gloo.  The one-sided transport polls arrival flags on the GPU,
     # and N processes polling on ONE shared GPU crawl from time slice to time slice; it is covered on small inputs by
     # tests/test_gpu_two_process.py.)
-    d = _run("--gpus", str(ranks), "--no-cpu-baseline", HEPT_BENCH_BACKEND="gloo", HEPT_BENCH_EXCHANGE="all_to_all",
+    d = _run("--full", "--gpus", str(ranks), "--no-cpu-baseline", HEPT_BENCH_BACKEND="gloo", HEPT_BENCH_EXCHANGE="all_to_all",
              HEPT_EXCHANGE="torch")
     assert KEYS <= set(d) and d["n_gpus"] == ranks and d["scaling"] == "weak"
     assert f"({3 * ranks} total)" in d["config"]["workload"] and "all_to_all" in d["config"]["parallelism"]
@@ -184,7 +202,7 @@ def test_bench_as_a_rank_under_torch_distributed_run(gpu_device):
         env.pop(k, None)
     run = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29643", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+                          "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.strip().startswith("{")]

@@ -20,8 +20,8 @@ for prec in fp32 bf16; do
   # slows the host's launches, which shows up as gaps between kernels, not inside them)
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_$prec -o ks -- python3 $R/bench.py --precision $prec --no-cpu-baseline --no-extra > $O/bench_$prec.log 2>&1
 done
-# the driver's command (default precision; carries the fp32, mixed16 and c4 sub-records and the CPU baseline)
-python3 $R/bench.py 2>/dev/null | grep '^{' | tail -1 > $O/bench.json
+# the whole line (default precision; --full adds the fp32, mixed16, c4 and per-configuration records and the CPU baseline)
+python3 $R/bench.py --full 2>/dev/null | grep '^{' | tail -1 > $O/bench.json
 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > $O/bench_driver_cmd.json
 python3 $R/bench.py --stages --no-cpu-baseline --no-extra 2>&1 | grep "stage ms" > $O/stage_ms.txt
 python3 $R/bench.py --stages --no-cpu-baseline --no-extra --precision fp32 2>&1 | grep "stage ms" >> $O/stage_ms.txt
