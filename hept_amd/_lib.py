@@ -12,8 +12,9 @@ from ctypes import c_float, c_int, c_int64, c_size_t, c_void_p
 # (kept in step with hept_amd/build.py, which is not imported here so that `python -m hept_amd.build` runs clean)
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libhept_hip.so")
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 PREC_F32, PREC_BF16, PREC_MIXED16, PREC_F32_MFMA, PREC_F32_DIFF = 0, 1, 2, 3, 4
+IN_F32, IN_BF16, IN_F16 = 0, 1, 2   # HEPT_IN_*: element type of q, k, v at the *_in entry points
 ROW = 32
 MAX_TABLES = 8
 MAX_BLOCK = 256
@@ -35,6 +36,7 @@ SIGNATURES = {
     "hept_workspace_bytes": (c_size_t, [c_int] * 7),
     "hept_rpe_scale": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "hept_prep_hash": (c_int, [_P] * 7 + [c_int] * 9 + [_P] * 6),
+    "hept_prep_hash_in": (c_int, [_P] * 3 + [c_int] + [_P] * 4 + [c_int] * 9 + [_P] * 6),
     "hept_sort_workspace_bytes": (c_size_t, [c_int] * 3),
     "hept_sort_tables": (c_int, [_P] * 4 + [c_int] * 5 + [_P] * 4),
     "hept_sort_tables_src": (c_int, [_P] * 6 + [c_int] * 5 + [_P] * 4),
@@ -53,6 +55,8 @@ SIGNATURES = {
     "hept_combine_out": (c_int, [_P] + [c_int] * 7 + [_P] * 4),
     "hept_forward": (c_int, [_P] * 9 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
     "hept_forward_partial": (c_int, [_P] * 7 + [c_int] * 11 + [_P, c_size_t, _P, _P]),
+    "hept_forward_in": (c_int, [_P] * 3 + [c_int] + [_P] * 6 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
+    "hept_forward_partial_in": (c_int, [_P] * 3 + [c_int] + [_P] * 4 + [c_int] * 11 + [_P, c_size_t, _P, _P]),
     "hept_prep_hash_fused": (c_int, [_P] * 3 + [c_float] + [_P] * 7 + [c_int] * 9 + [_P] * 6),
     "hept_combine_ffn": (c_int, [_P] + [c_int] * 7 + [_P] * 5 + [c_float] + [_P] * 6),
     "hept_attn_block_forward": (c_int, [_P] * 4 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
@@ -62,6 +66,8 @@ SIGNATURES = {
     "hept_combine_bwd": (c_int, [_P] * 3 + [c_int] * 3 + [_P] * 4 + [c_size_t, _P]),
     "hept_forward_src": (c_int, [_P] * 7 + [c_int] + [_P] * 4 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
     "hept_forward_partial_src": (c_int, [_P] * 7 + [c_int] + [_P] * 2 + [c_int] * 11 + [_P, c_size_t, _P, _P]),
+    "hept_forward_src_in": (c_int, [_P] * 3 + [c_int] + [_P] * 4 + [c_int] + [_P] * 4 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
+    "hept_forward_partial_src_in": (c_int, [_P] * 3 + [c_int] + [_P] * 4 + [c_int] + [_P] * 2 + [c_int] * 11 + [_P, c_size_t, _P, _P]),
     "hept_block_attn_bwd": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),
     "hept_block_attn_bwd_f32mfma": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),
     "hept_block_attn_bwd_bf16": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),

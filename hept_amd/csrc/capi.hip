@@ -105,7 +105,8 @@ static inline bool direct_v_pays(int B) { return B > 128; }
 
 // everything before the block attention, for tables [t0, t0 + Tl): parameter math, augmented rows + hashes, sort.
 // Leaves qhat / kvhat and the permutations (w.pos: q then k, (Tl, H, N) each) in the workspace.
-int run_begin(const float* q, const float* k, const float* v, const float* coords, const int64_t* codes,
+// q, k, v: element type in_dtype (HEPT_IN_*); 16-bit rows are widened in registers by the row builder and the riders
+int run_begin(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
               const GeoShift& geo, const float* w_rpe, const float* alpha, int N, int H, int D, int C, int K, int T,
               int t0, int Tl, int precision, const Workspace& w, void* stream, VSrc* dv = nullptr) {
     hipStream_t st = (hipStream_t)stream;
@@ -132,11 +133,14 @@ int run_begin(const float* q, const float* k, const float* v, const float* coord
     // same sectors as a padded kvhat row) and the bucket sort loses its riders -- 46 MB read + 61.5 MB written per call
     // at tracking-60k (HEPT_NO_DIRECT_V=1: A/B measurements; read once)
     static const bool no_direct_v = [] { const char* e = getenv("HEPT_NO_DIRECT_V"); return e && *e && *e != '0'; }();
-    const bool direct_v = dv && precision == HEPT_PREC_F32 && D % 4 == 0 && !no_direct_v &&
+    // (the split kernel reads f32 pieces of v: 16-bit inputs get their value rows from the riders or the v role)
+    const bool direct_v = dv && precision == HEPT_PREC_F32 && D % 4 == 0 && !no_direct_v && in_dtype == HEPT_IN_F32 &&
                           (reinterpret_cast<uintptr_t>(v) & 15) == 0;
-    if (dv) *dv = direct_v ? VSrc{v, raw_size} : VSrc{};
-    const bool ride = !direct_v && Tl <= HEPT_MAX_TABLES && (Tl >= 2 || f32_rows || force_ride) && hept_sort_carries_rows(N, H, D) && !row_riders_off();
-    const HeptRowsJob job{v, w.kvhat, N, raw_size, H, D, precision};
+    if (dv) *dv = direct_v ? VSrc{reinterpret_cast<const float*>(v), raw_size} : VSrc{};
+    // (the riders fetch 16-bit rows as 8-byte pieces; a base the generic row builder accepts at 2 bytes keeps the v role)
+    const bool ride_base = in_dtype == HEPT_IN_F32 || (reinterpret_cast<uintptr_t>(v) & 7) == 0;
+    const bool ride = !direct_v && ride_base && Tl <= HEPT_MAX_TABLES && (Tl >= 2 || f32_rows || force_ride) && hept_sort_carries_rows(N, H, D) && !row_riders_off();
+    const HeptRowsJob job{v, w.kvhat, N, raw_size, H, D, precision, in_dtype};
     const HeptRowsJob* rows = ride ? &job : nullptr;
     for (int c0 = 0; c0 < Tl; c0 += HEPT_MAX_TABLES) {   // chunks of tables (the rows are rewritten identically)
         const int tc = Tl - c0 < HEPT_MAX_TABLES ? Tl - c0 : HEPT_MAX_TABLES;
@@ -146,7 +150,7 @@ int run_begin(const float* q, const float* k, const float* v, const float* coord
         hept_sort_zero_block(w.sort_ws, N, H, tc, &zptr, &zbytes);
         rc = hept_prep_hash_rpe(q, k, v, coords, w_rpe, K, alpha, codes, N, raw_size, H, D, C, T,
                                 t0 + c0, tc, precision, w.qhat, w.kvhat, w.qproj, w.kproj, w.minmax, stream,
-                                (ride || direct_v) ? 2 : 3, zptr, zbytes);
+                                (ride || direct_v) ? 2 : 3, zptr, zbytes, in_dtype);
         if (rc) return rc;
         if (c0 == 0) prof_mark(1, st);
         // the sort writes one (2, tc, H, N) array: straight into w.pos when the call is a single chunk
@@ -169,11 +173,11 @@ int run_begin(const float* q, const float* k, const float* v, const float* coord
 }
 
 // stages shared by hept_forward / hept_forward_partial; leaves per-table partials in `part`
-int run_tables(const float* q, const float* k, const float* v, const float* coords, const int64_t* codes,
+int run_tables(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
                const GeoShift& geo, const float* w_rpe, const float* alpha, int N, int H, int D, int C, int K, int T,
                int t0, int Tl, int B, int precision, const Workspace& w, float* part, void* stream) {
     VSrc dv;
-    int rc = run_begin(q, k, v, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream,
+    int rc = run_begin(q, k, v, in_dtype, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream,
                        direct_v_pays(B) ? &dv : nullptr);
     if (rc) return rc;
     rc = hept_block_attn_heads_push(w.qhat, w.kvhat, w.pos, w.pos + (size_t)Tl * H * N, N, H, D, Tl, B, precision, 0, H, H,
@@ -189,7 +193,7 @@ void hept_prof_mark_sort_mid(void* stream) {
     if (g_prof.mode == 2 && prof_active() && !g_prof.mid[g_prof.n_calls]) prof_mark(PROF_SORT_MID, (hipStream_t)stream);
 }
 
-extern "C" int hept_abi_version(void) { return 21; }
+extern "C" int hept_abi_version(void) { return 22; }
 
 extern "C" int hept_part_precision(int precision, int D) {
     return (precision != HEPT_PREC_F32 && precision != HEPT_PREC_F32_MFMA && precision != HEPT_PREC_F32_DIFF && D == 24) ? HEPT_PREC_BF16 : HEPT_PREC_F32;
@@ -211,16 +215,17 @@ extern "C" size_t hept_workspace_bytes(int N, int H, int D, int C, int Tl, int B
 }
 
 namespace {
-int forward_impl(const float* q, const float* k, const float* v, const float* coords, const int64_t* codes,
+int forward_impl(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
                  const GeoShift& geo, const float* w_rpe, const float* alpha, const float* out_weight,
                  const float* out_bias, int N, int H, int D, int C, int K, int T, int B, int precision,
                  void* workspace, size_t workspace_bytes, float* out, void* stream) {
     if (!q || !k || !v || !coords || !w_rpe || !alpha || !out_weight || !workspace || !out) return HEPT_ERR_ARG;
+    if (in_dtype != HEPT_IN_F32 && in_dtype != HEPT_IN_BF16 && in_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
     int rc = hept_check_shape(N, H, D, C, T, B);
     if (rc) return rc;
     const Workspace w = carve(workspace, N, H, C, T, precision);
     if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
-    rc = run_tables(q, k, v, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, 0, T, B, precision, w, w.part,
+    rc = run_tables(q, k, v, in_dtype, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, 0, T, B, precision, w, w.part,
                     stream);
     if (rc) return rc;
     rc = hept_combine_out(w.part, hept_part_precision(precision, D), T, N, H, D, 0, N, out_weight, out_bias, out,
@@ -230,11 +235,12 @@ int forward_impl(const float* q, const float* k, const float* v, const float* co
     return rc;
 }
 
-int forward_partial_impl(const float* q, const float* k, const float* v, const float* coords, const int64_t* codes,
+int forward_partial_impl(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
                          const GeoShift& geo, const float* w_rpe, const float* alpha, int N, int H, int D, int C,
                          int K, int T, int t0, int Tl, int B, int precision, int acc_precision, void* workspace,
                          size_t workspace_bytes, float* acc, void* stream) {
     if (!q || !k || !v || !coords || !w_rpe || !alpha || !workspace || !acc) return HEPT_ERR_ARG;
+    if (in_dtype != HEPT_IN_F32 && in_dtype != HEPT_IN_BF16 && in_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
     int rc = hept_check_shape(N, H, D, C, Tl, B);
     if (rc) return rc;
     if (t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
@@ -245,7 +251,7 @@ int forward_partial_impl(const float* q, const float* k, const float* v, const f
     const int pprec = hept_part_precision(precision, D);
     const bool direct = Tl == 1 && pprec == acc_precision;
     float* part = direct ? acc : w.part;
-    rc = run_tables(q, k, v, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B, precision, w, part,
+    rc = run_tables(q, k, v, in_dtype, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B, precision, w, part,
                     stream);
     if (!rc && !direct) rc = hept_reduce_tables(w.part, pprec, Tl, N, H, D, acc, acc_precision, stream);
     prof_mark(4, (hipStream_t)stream);
@@ -258,9 +264,17 @@ extern "C" int hept_forward(const float* q, const float* k, const float* v, cons
                             const int64_t* codes, const float* w_rpe, const float* alpha, const float* out_weight,
                             const float* out_bias, int N, int H, int D, int C, int K, int T, int B, int precision,
                             void* workspace, size_t workspace_bytes, float* out, void* stream) {
+    return hept_forward_in(q, k, v, HEPT_IN_F32, coords, codes, w_rpe, alpha, out_weight, out_bias, N, H, D, C, K, T, B,
+                           precision, workspace, workspace_bytes, out, stream);
+}
+
+extern "C" int hept_forward_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                               const int64_t* codes, const float* w_rpe, const float* alpha, const float* out_weight,
+                               const float* out_bias, int N, int H, int D, int C, int K, int T, int B, int precision,
+                               void* workspace, size_t workspace_bytes, float* out, void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return forward_impl(q, k, v, coords, codes, GeoShift{}, w_rpe, alpha, out_weight, out_bias, N, H, D, C, K, T, B,
-                        precision, workspace, workspace_bytes, out, stream);
+    return forward_impl(q, k, v, in_dtype, coords, codes, GeoShift{}, w_rpe, alpha, out_weight, out_bias, N, H, D, C, K, T,
+                        B, precision, workspace, workspace_bytes, out, stream);
 }
 
 extern "C" int hept_forward_partial(const float* q, const float* k, const float* v, const float* coords,
@@ -268,8 +282,17 @@ extern "C" int hept_forward_partial(const float* q, const float* k, const float*
                                     int D, int C, int K, int T, int t0, int Tl, int B, int precision,
                                     int acc_precision, void* workspace, size_t workspace_bytes, float* acc,
                                     void* stream) {
+    return hept_forward_partial_in(q, k, v, HEPT_IN_F32, coords, codes, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B, precision,
+                                   acc_precision, workspace, workspace_bytes, acc, stream);
+}
+
+extern "C" int hept_forward_partial_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                                       const int64_t* codes, const float* w_rpe, const float* alpha, int N, int H,
+                                       int D, int C, int K, int T, int t0, int Tl, int B, int precision,
+                                       int acc_precision, void* workspace, size_t workspace_bytes, float* acc,
+                                       void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return forward_partial_impl(q, k, v, coords, codes, GeoShift{}, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B,
+    return forward_partial_impl(q, k, v, in_dtype, coords, codes, GeoShift{}, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B,
                                 precision, acc_precision, workspace, workspace_bytes, acc, stream);
 }
 
@@ -278,9 +301,18 @@ extern "C" int hept_forward_src(const float* q, const float* k, const float* v, 
                                 const float* w_rpe, const float* alpha, const float* out_weight,
                                 const float* out_bias, int N, int H, int D, int C, int K, int T, int B,
                                 int precision, void* workspace, size_t workspace_bytes, float* out, void* stream) {
+    return hept_forward_src_in(q, k, v, HEPT_IN_F32, coords, eta_idx, phi_idx, cfac, raw_size, w_rpe, alpha, out_weight,
+                               out_bias, N, H, D, C, K, T, B, precision, workspace, workspace_bytes, out, stream);
+}
+
+extern "C" int hept_forward_src_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                                   const float* eta_idx, const float* phi_idx, const float* cfac, int raw_size,
+                                   const float* w_rpe, const float* alpha, const float* out_weight,
+                                   const float* out_bias, int N, int H, int D, int C, int K, int T, int B,
+                                   int precision, void* workspace, size_t workspace_bytes, float* out, void* stream) {
     if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
     if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return forward_impl(q, k, v, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe, alpha,
+    return forward_impl(q, k, v, in_dtype, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe, alpha,
                         out_weight, out_bias, N, H, D, C, K, T, B, precision, workspace, workspace_bytes, out, stream);
 }
 
@@ -289,11 +321,22 @@ extern "C" int hept_forward_partial_src(const float* q, const float* k, const fl
                                         const float* w_rpe, const float* alpha, int N, int H, int D, int C, int K,
                                         int T, int t0, int Tl, int B, int precision, int acc_precision,
                                         void* workspace, size_t workspace_bytes, float* acc, void* stream) {
+    return hept_forward_partial_src_in(q, k, v, HEPT_IN_F32, coords, eta_idx, phi_idx, cfac, raw_size, w_rpe, alpha, N, H,
+                                       D, C, K, T, t0, Tl, B, precision, acc_precision, workspace, workspace_bytes, acc,
+                                       stream);
+}
+
+extern "C" int hept_forward_partial_src_in(const void* q, const void* k, const void* v, int in_dtype,
+                                           const float* coords, const float* eta_idx, const float* phi_idx,
+                                           const float* cfac, int raw_size, const float* w_rpe, const float* alpha,
+                                           int N, int H, int D, int C, int K, int T, int t0, int Tl, int B,
+                                           int precision, int acc_precision, void* workspace, size_t workspace_bytes,
+                                           float* acc, void* stream) {
     if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
     if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return forward_partial_impl(q, k, v, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe, alpha, N,
-                                H, D, C, K, T, t0, Tl, B, precision, acc_precision, workspace, workspace_bytes, acc,
-                                stream);
+    return forward_partial_impl(q, k, v, in_dtype, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe,
+                                alpha, N, H, D, C, K, T, t0, Tl, B, precision, acc_precision, workspace, workspace_bytes,
+                                acc, stream);
 }
 
 namespace {
@@ -307,7 +350,7 @@ int partial_begin_impl(const float* q, const float* k, const float* v, const flo
     if (t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
     const Workspace w = carve(workspace, N, H, C, Tl, precision);
     if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
-    return run_begin(q, k, v, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream);
+    return run_begin(q, k, v, HEPT_IN_F32, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream);
 }
 }  // namespace
 
@@ -412,7 +455,7 @@ int sharded_steps(hept_comm* comm, const float* q, const float* k, const float* 
     char* send = reinterpret_cast<char*>(xbuf);
     char* recv = one_sided ? comm->p2p_local + lay.recv_off : send + up256((size_t)n_pad * H * row);
     VSrc dv;
-    int rc = run_begin(q, k, v, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream,
+    int rc = run_begin(q, k, v, HEPT_IN_F32, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream,
                        direct_v_pays(B) ? &dv : nullptr);
     if (rc) return rc;
     const int pprec = hept_part_precision(precision, D);

@@ -93,6 +93,33 @@ __device__ __forceinline__ unsigned int hept_pack_f16(float lo, float hi) {
 __device__ __forceinline__ float hept_f16_lo(unsigned int w) { return (float)__builtin_bit_cast(hept_f16x2, w)[0]; }
 __device__ __forceinline__ float hept_f16_hi(unsigned int w) { return (float)__builtin_bit_cast(hept_f16x2, w)[1]; }
 
+// ---- 16-bit q, k, v (HEPT_IN_BF16 / HEPT_IN_F16) widened in registers: every such value is an f32 value, so the row
+// builder and the riders compute on exactly what `.float()` would have handed them.  A dword holds elements 2i (low
+// half) and 2i + 1.  bf16: the f32 with the same upper 16 bits.  fp16: v_cvt_f32_f16, exact for every finite value --
+// the kernels run with fp16 denormals on (hipcc's default mode, .amdhsa_float_denorm_mode_16_64 3), so fp16 subnormals
+// widen to their (normal) f32 values instead of zero.
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+template <int IN>
+__device__ __forceinline__ float hept_in_lo(unsigned int w) {
+    if constexpr (IN == HEPT_IN_BF16) return hept_bf16_lo(w);
+    else return hept_f16_lo(w);
+}
+template <int IN>
+__device__ __forceinline__ float hept_in_hi(unsigned int w) {
+    if constexpr (IN == HEPT_IN_BF16) return hept_bf16_hi(w);
+    else return hept_f16_hi(w);
+}
+template <int IN>
+__device__ __forceinline__ f32x4 hept_widen4(unsigned int w0, unsigned int w1) {   // 4 consecutive elements
+    return f32x4{hept_in_lo<IN>(w0), hept_in_hi<IN>(w0), hept_in_lo<IN>(w1), hept_in_hi<IN>(w1)};
+}
+// one element of a 16-bit array (2-byte aligned), or of an f32 array
+template <int IN>
+__device__ __forceinline__ float hept_in_elem(const void* x, size_t i) {
+    if constexpr (IN == HEPT_IN_F32) return reinterpret_cast<const float*>(x)[i];
+    else return hept_in_lo<IN>(reinterpret_cast<const unsigned short*>(x)[i]);
+}
+
 // Row of the 32x32 MFMA accumulator held in register r by lane-half hh
 // (C/D layout of v_mfma_f32_32x32x*: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)).
 __device__ __forceinline__ int hept_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
@@ -210,11 +237,13 @@ __device__ __forceinline__ unsigned int hept_wave_max(unsigned int x) {
 // ---- entry points shared between translation units (not part of the C ABI) ---------------------------------------------
 // hept_prep_hash / hept_prep_hash_fused with the RPE weight math folded in (prep_hash.hip): K == 0: `sqrt_w` is
 // sqrt_w (H, C); K > 0: it is w_rpe.weight (H*D, (C-1)*K) and the kernels compute the scale in their prologue.
-int hept_prep_hash_rpe(const float* q, const float* k, const float* v, const float* coords, const float* sqrt_w, int K,
+// q, k, v: (N, H*D) of element type in_dtype (HEPT_IN_*; alignment contract: include/hept_hip.h, the *_in entry points)
+int hept_prep_hash_rpe(const void* q, const void* k, const void* v, const float* coords, const float* sqrt_w, int K,
                        const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T, int t0,
                        int Tl, int precision, void* qhat, void* kvhat, float* qproj, float* kproj, float* minmax,
                        void* stream, int roles = 3,   // roles == 2: q and k rows + hashes only (the v rows: HeptRowsJob)
-                       void* zero_ptr = nullptr, size_t zero_bytes = 0);   // scratch the launch clears on its way (hept_sort_zero_block)
+                       void* zero_ptr = nullptr, size_t zero_bytes = 0,   // scratch the launch clears on its way (hept_sort_zero_block)
+                       int in_dtype = HEPT_IN_F32);
 int hept_prep_hash_fused_rpe(const float* x, const float* norm_w, const float* norm_b, float eps, const float* w_q,
                              const float* w_k, const float* w_v, const float* coords, const float* sqrt_w, int K,
                              const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T,
@@ -225,9 +254,10 @@ int hept_prep_hash_fused_rpe(const float* x, const float* norm_w, const float* n
 // hept_sort_tables_src_rows with a job description write them.  hept_sort_carries_rows: the sort of N-key segments has
 // such a launch (segments longer than the one-workgroup sort) and the rows split into 16-B pieces (D % 4 == 0).
 struct HeptRowsJob {
-    const float* v;   // (N, H * D) fp32
+    const void* v;    // (N, H * D) of in_dtype; 16-bit: 8-byte aligned (the riders fetch 8-byte pieces)
     void* kvhat;
     int N, raw_size, H, D, precision;
+    int in_dtype;     // HEPT_IN_*
 };
 bool hept_sort_carries_rows(int N, int H, int D);
 // zeroed: the block hept_sort_zero_block names has been zeroed on this stream by the caller (the row builder of the same

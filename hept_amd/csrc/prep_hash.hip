@@ -163,8 +163,11 @@ struct FusedIn {
 };
 constexpr int FUSED_WPITCH = 24 * 24 + 4;  // head pitch = 4 (mod 32) dwords: the 8 heads' 16-B reads hit 8 distinct bank groups
 
-template <int D, int C, int TILE, int ROLE, int TMAX, bool FUSED = false>
-__device__ __forceinline__ void prep_role(const float* __restrict__ x, const float* __restrict__ coords,
+// IN (HEPT_IN_*): element type of x.  16-bit inputs: the wave's run is 3 KiB at H*D = 192, fetched as 16-B pieces of 8
+// elements (3 / 2 / 1 loads per lane at D = 24 / 16 / 8), each widened in registers to the two f32 chunks it holds and
+// written to their two LDS slots -- everything after the LDS read-back is the f32 code.
+template <int D, int C, int TILE, int ROLE, int TMAX, bool FUSED = false, int IN = HEPT_IN_F32>
+__device__ __forceinline__ void prep_role(const void* __restrict__ x_, const float* __restrict__ coords,
                                           const float* __restrict__ sw_s, const float* __restrict__ alpha_s,
                                           const int64_t* __restrict__ codes, int N, int raw_size, int t0, int Tl,
                                           char* __restrict__ out_rows, float* __restrict__ proj,
@@ -179,7 +182,11 @@ __device__ __forceinline__ void prep_role(const float* __restrict__ x, const flo
     constexpr int ROWB = ROLE == 0 ? QROW : 2 * QROW;   // row pitch of the destination array
     constexpr int ROWOFF = ROLE == 2 ? QROW : 0;        // v lives in the second half of a kvhat row
     constexpr int CH = QROW / 16;                       // 16-B chunks per finished row
-    constexpr int LOADS = PREP_POINTS * HD / 4 / HEPT_WAVE;  // input chunks per lane (6)
+    constexpr bool IN16 = IN != HEPT_IN_F32;
+    static_assert(!(FUSED && IN16), "the fused row builder reads f32 activations");
+    // input pieces of 16 B per lane: 4 floats (6 at D = 24), or 8 16-bit elements = f32 chunks 2c and 2c + 1 (3)
+    constexpr int LOADS = PREP_POINTS * HD / (IN16 ? 8 : 4) / HEPT_WAVE;
+    static_assert(D4 % 2 == 0 || !IN16, "an 8-element piece must not straddle a head row");
     constexpr int ROW4 = D4 | 1;                        // LDS pitch of an input row in 16-B slots (odd)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int h = lane & 7, p = lane >> 3;
@@ -189,7 +196,7 @@ __device__ __forceinline__ void prep_role(const float* __restrict__ x, const flo
     int wslot[LOADS];  // chunk c of the tile belongs to row c / D4 (= the lane that reads it), slot c % D4
 #pragma unroll
     for (int j = 0; j < LOADS; ++j) {
-        const int c = j * 64 + lane;
+        const int c = (j * 64 + lane) * (IN16 ? 2 : 1);   // 16-bit piece: its first f32 chunk (D4 even: the second is the next slot)
         wslot[j] = (c / D4) * ROW4 + (c % D4);
     }
 
@@ -221,7 +228,7 @@ __device__ __forceinline__ void prep_role(const float* __restrict__ x, const flo
         f32x4 xr[D4];
         if constexpr (FUSED) {
             float xv[D];
-            const f32x4* xs = reinterpret_cast<const f32x4*>(x + (size_t)(live ? n : n0) * D);
+            const f32x4* xs = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x_) + (size_t)(live ? n : n0) * D);
 #pragma unroll
             for (int j = 0; j < D4; ++j) {
                 const f32x4 v4 = xs[j];
@@ -252,8 +259,22 @@ __device__ __forceinline__ void prep_role(const float* __restrict__ x, const flo
                 // keep the 144 weight reads from being hoisted in front of the fma chains (they would need ~600 VGPRs)
                 __builtin_amdgcn_sched_barrier(0);
             }
+        } else if constexpr (IN16) {
+            const u32x4* src = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(x_) + (size_t)n0 * HD);
+            const int valid_pieces = rows * (HD / 8);
+            u32x4 xin[LOADS];
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j)
+                xin[j] = (j * 64 + lane < valid_pieces) ? hept_ld<HEPT_NT_PREP_IN>(src + j * 64 + lane) : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j) {
+                buf[wslot[j]] = hept_widen4<IN>(xin[j][0], xin[j][1]);
+                buf[wslot[j] + 1] = hept_widen4<IN>(xin[j][2], xin[j][3]);
+            }
+#pragma unroll
+            for (int j = 0; j < D4; ++j) xr[j] = buf[lane * ROW4 + j];
         } else {
-            const f32x4* src = reinterpret_cast<const f32x4*>(x + (size_t)n0 * HD);
+            const f32x4* src = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x_) + (size_t)n0 * HD);
             const int valid_chunks = rows * (HD / 4);
             f32x4 xin[LOADS];
 #pragma unroll
@@ -466,11 +487,11 @@ inline int prep_wgs(int N, int roles = 3) {
 
 // (fp16 q^/k^ rows, 4 table slots: left alone the allocation takes 135 VGPRs = 3 waves per SIMD where the bf16 build
 //  takes 128; held to 4 waves like it -- the LDS allows 4 workgroups per CU)
-template <int D, int C, int TILE, int TMAX>
+template <int D, int C, int TILE, int TMAX, int IN>
 __global__ __launch_bounds__(PREP_THREADS)
 __attribute__((amdgpu_waves_per_eu((TILE == HEPT_PREC_MIXED16 && TMAX == 4) ? 4 : 1, (TILE == HEPT_PREC_MIXED16 && TMAX == 4) ? 4 : 8)))
 void prep_hash_kernel(
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+    const void* __restrict__ q, const void* __restrict__ k, const void* __restrict__ v,
     const float* __restrict__ coords, const float* __restrict__ sqrt_w, int K, const float* __restrict__ alpha,
     const int64_t* __restrict__ codes, int N, int raw_size, int T, int t0, int Tl, void* __restrict__ qhat_,
     void* __restrict__ kvhat_, float* __restrict__ qproj, float* __restrict__ kproj, float* __restrict__ minmax,
@@ -497,13 +518,13 @@ void prep_hash_kernel(
         __syncthreads();
     }
     if (role == 0)
-        prep_role<D, C, TILE, 0, TMAX>(q, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(qhat_), qproj,
+        prep_role<D, C, TILE, 0, TMAX, false, IN>(q, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(qhat_), qproj,
                                  red_s, tile_s, minmax, blockIdx.x, cmax_s);
     else if (role == 1)
-        prep_role<D, C, TILE, 1, TMAX>(k, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_), kproj,
+        prep_role<D, C, TILE, 1, TMAX, false, IN>(k, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_), kproj,
                                  red_s, tile_s, minmax, PREP_SLOTS_PER_ROLE + blockIdx.x, cmax_s);
     else
-        prep_role<D, C, TILE, 2, TMAX>(v, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_), nullptr,
+        prep_role<D, C, TILE, 2, TMAX, false, IN>(v, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_), nullptr,
                                  red_s, tile_s, minmax, 0, cmax_s);
 }
 
@@ -582,24 +603,31 @@ int launch_prep_fused(const float* x, const float* ln_w, const float* ln_b, floa
 }
 
 template <int D, int C>
-int launch_prep(const float* q, const float* k, const float* v, const float* coords, const float* sqrt_w, int K,
+int launch_prep(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const float* sqrt_w, int K,
                 const float* alpha, const int64_t* codes, int N, int raw_size, int T, int t0, int Tl, int precision,
                 void* qhat, void* kvhat, float* qproj, float* kproj, float* minmax, hipStream_t st, int roles, ZeroJob zero) {
     // q- and k-role workgroups each write one of the HEPT_PREP_GRID partial slots the sort kernel reduces
     const dim3 grid(prep_wgs(N, roles), roles);
     // table slots of the kernel (accumulators, alpha slab): 4 for the usual 1-4 tables per call, else HEPT_MAX_TABLES
-#define HEPT_PREP_LAUNCH(TILE, TMAX)                                                                                 \
-    hipLaunchKernelGGL((prep_hash_kernel<D, C, TILE, TMAX>), grid, dim3(PREP_THREADS), 0, st, q, k, v, coords, sqrt_w, \
+#define HEPT_PREP_LAUNCH(TILE, TMAX, IN)                                                                                 \
+    hipLaunchKernelGGL((prep_hash_kernel<D, C, TILE, TMAX, IN>), grid, dim3(PREP_THREADS), 0, st, q, k, v, coords, sqrt_w, \
                        K, alpha, codes, N, raw_size, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero)
+#define HEPT_PREP_IN(TILE, TMAX)                                                                                     \
+    do {                                                                                                             \
+        if (in_dtype == HEPT_IN_BF16) HEPT_PREP_LAUNCH(TILE, TMAX, HEPT_IN_BF16);                                    \
+        else if (in_dtype == HEPT_IN_F16) HEPT_PREP_LAUNCH(TILE, TMAX, HEPT_IN_F16);                                 \
+        else HEPT_PREP_LAUNCH(TILE, TMAX, HEPT_IN_F32);                                                              \
+    } while (0)
 #define HEPT_PREP_TILE(TILE)                                                                                         \
     do {                                                                                                             \
-        if (Tl <= 4) HEPT_PREP_LAUNCH(TILE, 4);                                                                      \
-        else HEPT_PREP_LAUNCH(TILE, HEPT_MAX_TABLES);                                                                \
+        if (Tl <= 4) HEPT_PREP_IN(TILE, 4);                                                                          \
+        else HEPT_PREP_IN(TILE, HEPT_MAX_TABLES);                                                                    \
     } while (0)
     if (precision == HEPT_PREC_BF16) HEPT_PREP_TILE(HEPT_PREC_BF16);
     else if (precision == HEPT_PREC_MIXED16) HEPT_PREP_TILE(HEPT_PREC_MIXED16);
     else HEPT_PREP_TILE(HEPT_PREC_F32);
 #undef HEPT_PREP_TILE
+#undef HEPT_PREP_IN
 #undef HEPT_PREP_LAUNCH
     return hept_launch_status();
 }
@@ -619,9 +647,10 @@ __device__ __forceinline__ float f32_from_ordered(unsigned int u) {
     return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
-template <int TILE>
+// IN (HEPT_IN_*): 16-bit rows are read with 2-byte loads (the row stride H*D*2 bytes may be odd in units of 4 bytes)
+template <int TILE, int IN>
 __global__ __launch_bounds__(PREP_THREADS) void prep_generic_kernel(
-    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+    const void* __restrict__ q, const void* __restrict__ k, const void* __restrict__ v,
     const float* __restrict__ coords, const float* __restrict__ sqrt_w, int K, const float* __restrict__ alpha,
     const int64_t* __restrict__ codes, int N, int raw_size, int H, int D, int C, int T, int t0, int Tl,
     void* __restrict__ qhat_, void* __restrict__ kvhat_, float* __restrict__ qproj, float* __restrict__ kproj,
@@ -650,7 +679,7 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_generic_kernel(
             for (int i = tid; i < H * C; i += PREP_THREADS) sw_s[i] = sqrt_w[i];
         __syncthreads();
     }
-    const float* x = role == 0 ? q : (role == 1 ? k : v);
+    const void* x = role == 0 ? q : (role == 1 ? k : v);
     char* out_rows = reinterpret_cast<char*>(role == 0 ? qhat_ : kvhat_);
     const int rowb = role == 0 ? QROW : 2 * QROW, rowoff = role == 2 ? QROW : 0;
     float* proj = role == 0 ? qproj : kproj;
@@ -664,7 +693,7 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_generic_kernel(
         for (int e = 0; e < 32; ++e) a[e] = 0.f;
 #pragma unroll
         for (int j = 0; j < 28; ++j)
-            if (j < D) a[j] = is_pad ? 0.f : x[(size_t)n * HD + h * D + j];
+            if (j < D) a[j] = is_pad ? 0.f : hept_in_elem<IN>(x, (size_t)n * HD + h * D + j);
         char* dst = out_rows + ((size_t)h * N + n) * rowb + rowoff;
         if (role == 2) {
 #pragma unroll
@@ -744,20 +773,25 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_generic_kernel(
     }
 }
 
-int launch_prep_generic(const float* q, const float* k, const float* v, const float* coords, const float* sqrt_w, int K,
+int launch_prep_generic(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const float* sqrt_w, int K,
                         const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T, int t0,
                         int Tl, int precision, void* qhat, void* kvhat, float* qproj, float* kproj, float* minmax,
                         hipStream_t st, int roles, ZeroJob zero) {
     const dim3 grid(HEPT_PREP_GRID / 2, roles);   // q- and k-role workgroups each own one partial slot
-    if (precision == HEPT_PREC_BF16)
-        hipLaunchKernelGGL((prep_generic_kernel<HEPT_PREC_BF16>), grid, dim3(PREP_THREADS), 0, st, q, k, v, coords, sqrt_w,
-                           K, alpha, codes, N, raw_size, H, D, C, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero);
-    else if (precision == HEPT_PREC_MIXED16)
-        hipLaunchKernelGGL((prep_generic_kernel<HEPT_PREC_MIXED16>), grid, dim3(PREP_THREADS), 0, st, q, k, v, coords, sqrt_w,
-                           K, alpha, codes, N, raw_size, H, D, C, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero);
-    else
-        hipLaunchKernelGGL((prep_generic_kernel<HEPT_PREC_F32>), grid, dim3(PREP_THREADS), 0, st, q, k, v, coords, sqrt_w,
-                           K, alpha, codes, N, raw_size, H, D, C, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero);
+#define HEPT_GENERIC_LAUNCH(TILE, IN)                                                                                  \
+    hipLaunchKernelGGL((prep_generic_kernel<TILE, IN>), grid, dim3(PREP_THREADS), 0, st, q, k, v, coords, sqrt_w, K, alpha, \
+                       codes, N, raw_size, H, D, C, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero)
+#define HEPT_GENERIC_TILE(TILE)                                                                                        \
+    do {                                                                                                               \
+        if (in_dtype == HEPT_IN_BF16) HEPT_GENERIC_LAUNCH(TILE, HEPT_IN_BF16);                                         \
+        else if (in_dtype == HEPT_IN_F16) HEPT_GENERIC_LAUNCH(TILE, HEPT_IN_F16);                                      \
+        else HEPT_GENERIC_LAUNCH(TILE, HEPT_IN_F32);                                                                   \
+    } while (0)
+    if (precision == HEPT_PREC_BF16) HEPT_GENERIC_TILE(HEPT_PREC_BF16);
+    else if (precision == HEPT_PREC_MIXED16) HEPT_GENERIC_TILE(HEPT_PREC_MIXED16);
+    else HEPT_GENERIC_TILE(HEPT_PREC_F32);
+#undef HEPT_GENERIC_TILE
+#undef HEPT_GENERIC_LAUNCH
     return hept_launch_status();
 }
 
@@ -781,11 +815,12 @@ extern "C" int hept_rpe_scale_bwd(const float* w_rpe, const float* d_sqrt_w, int
 
 // internal (common.h): K == 0: `sqrt_w` is sqrt_w (H, C); K > 0: it is w_rpe.weight (H*D, (C-1)*K) and every workgroup
 // of the launch computes the scale in its prologue (rpe_scale_lds)
-int hept_prep_hash_rpe(const float* q, const float* k, const float* v, const float* coords, const float* sqrt_w, int K,
+int hept_prep_hash_rpe(const void* q, const void* k, const void* v, const float* coords, const float* sqrt_w, int K,
                        const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T, int t0,
                        int Tl, int precision, void* qhat, void* kvhat, float* qproj, float* kproj, float* minmax,
-                       void* stream, int roles, void* zero_ptr, size_t zero_bytes) {
+                       void* stream, int roles, void* zero_ptr, size_t zero_bytes, int in_dtype) {
     if (roles != 2 && roles != 3) return HEPT_ERR_ARG;
+    if (in_dtype != HEPT_IN_F32 && in_dtype != HEPT_IN_BF16 && in_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
     if (zero_bytes % 4 != 0 || (zero_bytes && !zero_ptr) || zero_bytes > 0xFFFFFFFFull) return HEPT_ERR_ARG;
     const ZeroJob zero{reinterpret_cast<unsigned int*>(zero_ptr), (unsigned int)(zero_bytes / 4)};
     if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
@@ -798,10 +833,15 @@ int hept_prep_hash_rpe(const float* q, const float* k, const float* v, const flo
     if (precision != HEPT_PREC_F32 && precision != HEPT_PREC_BF16 && precision != HEPT_PREC_MIXED16)
         return HEPT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
+    // 16-bit rows: the tuned kernels fetch 16-byte pieces, the generic one 2-byte elements
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v);
+    const bool in16 = in_dtype != HEPT_IN_F32;
 #define HEPT_PREP_CASE(DD, CC)                                                                             \
-    if (H == 8 && D == DD && C == CC)                                                                      \
-        return launch_prep<DD, CC>(q, k, v, coords, sqrt_w, K, alpha, codes, N, raw_size, T, t0, Tl, precision, \
-                                   qhat, kvhat, qproj, kproj, minmax, st, roles, zero);
+    if (H == 8 && D == DD && C == CC) {                                                                    \
+        if (in16 && (bases & 15)) return HEPT_ERR_ARG;                                                     \
+        return launch_prep<DD, CC>(q, k, v, in_dtype, coords, sqrt_w, K, alpha, codes, N, raw_size, T, t0, Tl, precision, \
+                                   qhat, kvhat, qproj, kproj, minmax, st, roles, zero);                    \
+    }
     HEPT_PREP_CASE(24, 6)
     HEPT_PREP_CASE(24, 4)
     HEPT_PREP_CASE(24, 2)
@@ -809,7 +849,8 @@ int hept_prep_hash_rpe(const float* q, const float* k, const float* v, const flo
     HEPT_PREP_CASE(16, 4)
     HEPT_PREP_CASE(8, 4)
 #undef HEPT_PREP_CASE
-    return launch_prep_generic(q, k, v, coords, sqrt_w, K, alpha, codes, N, raw_size, H, D, C, T, t0, Tl, precision, qhat,
+    if (in16 && (bases & 1)) return HEPT_ERR_ARG;
+    return launch_prep_generic(q, k, v, in_dtype, coords, sqrt_w, K, alpha, codes, N, raw_size, H, D, C, T, t0, Tl, precision, qhat,
                                kvhat, qproj, kproj, minmax, st, roles, zero);
 }
 
@@ -819,6 +860,14 @@ extern "C" int hept_prep_hash(const float* q, const float* k, const float* v, co
                               float* qproj, float* kproj, float* minmax, void* stream) {
     return hept_prep_hash_rpe(q, k, v, coords, sqrt_w, 0, alpha, codes, N, raw_size, H, D, C, T, t0, Tl, precision, qhat,
                               kvhat, qproj, kproj, minmax, stream, 3, nullptr, 0);
+}
+
+extern "C" int hept_prep_hash_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                                 const float* sqrt_w, const float* alpha, const int64_t* codes, int N, int raw_size,
+                                 int H, int D, int C, int T, int t0, int Tl, int precision, void* qhat, void* kvhat,
+                                 float* qproj, float* kproj, float* minmax, void* stream) {
+    return hept_prep_hash_rpe(q, k, v, coords, sqrt_w, 0, alpha, codes, N, raw_size, H, D, C, T, t0, Tl, precision, qhat,
+                              kvhat, qproj, kproj, minmax, stream, 3, nullptr, 0, in_dtype);
 }
 
 // internal (common.h): K as in hept_prep_hash_rpe

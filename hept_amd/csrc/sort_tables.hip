@@ -426,18 +426,96 @@ constexpr int BKT_WAVES = BKT_THREADS / HEPT_WAVE;
 // +4 us) or fewer (2: +1 us) are both worse than 3, and the q / k roles that stay behind run at 3.9 TB/s instead of
 // the three roles' 4.7 -- the v role was already filling their gaps.
 struct RowsJob {
-    const float* v;     // (N, H * D) fp32
+    const void* v;      // (N, H * D) fp32, or bf16 / fp16 at an 8-byte aligned base (`in`)
     char* kvhat;        // (H, N, 2 * qrow bytes): v half at byte qrow of a row
     int N, raw_size;    // rows >= raw_size are padding: v = 0 (src variant)
     int H, D4;          // D / 4
     int f32;            // 1: f32 tile rows (qrow = 128 B), 0: 16-bit rows (qrow = 64 B)
     int vy;             // grid rows (of gridDim.x workgroups each) that are riders; 0: none
+    int in;             // HEPT_IN_*: element type of v
 };
 #ifndef HEPT_ROWS_RIDERS
 #define HEPT_ROWS_RIDERS 3
 #endif
+// 16-bit v (IN = HEPT_IN_BF16 / HEPT_IN_F16): the same tiles, pieces and trips on half the input bytes.  A source address
+// is only 8-byte aligned in general (any D % 4 == 0), so the input moves as 8-byte loads of 4 elements: one per piece of
+// an f32 row, two per piece of a 16-bit row (half the load registers of the f32 input either way), widened at the store
+// (common.h: hept_widen4).  The 1.0 of column D travels as the input type's own 1.0 in the otherwise zero piece.  bf16
+// input into bf16 rows is a repack of the same bits (= hept_pack_bf16 of the widened values: bf16 -> f32 -> bf16 is
+// the identity).
+template <int H_, int IN>
+__device__ __forceinline__ void rows_rider16(const RowsJob& jb, unsigned int wg, unsigned int n_wgs) {
+    const unsigned int H = H_ ? H_ : (unsigned int)jb.H, D = 4u * (unsigned int)jb.D4, HD = H * D;
+    const unsigned int lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned int ntiles = ((unsigned int)jb.N + 7u) >> 3;
+    const unsigned int wave = wg * BKT_WAVES + wv, n_waves = n_wgs * BKT_WAVES;
+    const unsigned short* v16 = reinterpret_cast<const unsigned short*>(jb.v);
+    constexpr unsigned int ONE = IN == HEPT_IN_BF16 ? 0x3F80u : 0x3C00u;   // 1.0 in the low half of a dword
+    if (jb.f32) {
+        constexpr unsigned int PPR = 8, IT = 4;
+        for (unsigned int tile = wave; tile < ntiles; tile += n_waves) {
+            const unsigned int n0 = tile << 3;
+            for (unsigned int i0 = 0; i0 < H * 8 * PPR; i0 += 64 * IT) {
+                u32x2 x[IT];
+                unsigned int hd[IT], n[IT], k[IT];
+#pragma unroll
+                for (unsigned int u = 0; u < IT; ++u) {
+                    const unsigned int i = i0 + u * 64 + lane;
+                    k[u] = i & (PPR - 1);
+                    n[u] = n0 + ((i / PPR) & 7u);
+                    hd[u] = i / (8 * PPR);
+                    const bool data = hd[u] < H && n[u] < (unsigned int)jb.raw_size && 4 * k[u] < D;
+                    x[u] = data ? hept_ld<HEPT_NT_RIDER_IN32>(reinterpret_cast<const u32x2*>(v16 + (size_t)n[u] * HD + hd[u] * D + 4 * k[u]))
+                                : u32x2{4 * k[u] == D ? ONE : 0u, 0u};
+                }
+#pragma unroll
+                for (unsigned int u = 0; u < IT; ++u)
+                    if (hd[u] < H && n[u] < (unsigned int)jb.N)
+                        *reinterpret_cast<f32x4*>(jb.kvhat + ((size_t)hd[u] * jb.N + n[u]) * 256 + 128 + k[u] * 16) =
+                            hept_widen4<IN>(x[u][0], x[u][1]);
+            }
+        }
+    } else {
+        constexpr unsigned int PPR = 4, IT = 2;
+        for (unsigned int tile = wave; tile < ntiles; tile += n_waves) {
+            const unsigned int n0 = tile << 3;
+            for (unsigned int i0 = 0; i0 < H * 8 * PPR; i0 += 64 * IT) {
+                u32x2 x[IT][2];
+                unsigned int hd[IT], n[IT], k[IT];
+#pragma unroll
+                for (unsigned int u = 0; u < IT; ++u) {
+                    const unsigned int i = i0 + u * 64 + lane;
+                    k[u] = i & (PPR - 1);
+                    n[u] = n0 + ((i / PPR) & 7u);
+                    hd[u] = i / (8 * PPR);
+                    const bool row = hd[u] < H && n[u] < (unsigned int)jb.raw_size;
+                    const unsigned short* src = v16 + (size_t)n[u] * HD + hd[u] * D + 8 * k[u];
+                    x[u][0] = (row && 8 * k[u] < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const u32x2*>(src)) : u32x2{0u, 0u};
+                    x[u][1] = (row && 8 * k[u] + 4 < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const u32x2*>(src + 4)) : u32x2{0u, 0u};
+                    // the 1.0 of column D (D % 4 == 0: the first element of one of the two quads, which is not loaded)
+                    if (8 * k[u] == D) x[u][0][0] = ONE;
+                    if (8 * k[u] + 4 == D) x[u][1][0] = ONE;
+                }
+#pragma unroll
+                for (unsigned int u = 0; u < IT; ++u)
+                    if (hd[u] < H && n[u] < (unsigned int)jb.N) {
+                        u32x4 out = u32x4{x[u][0][0], x[u][0][1], x[u][1][0], x[u][1][1]};
+                        if constexpr (IN != HEPT_IN_BF16) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) out[j] = hept_pack_bf16(hept_in_lo<IN>(out[j]), hept_in_hi<IN>(out[j]));
+                        }
+                        *reinterpret_cast<u32x4*>(jb.kvhat + ((size_t)hd[u] * jb.N + n[u]) * 128 + 64 + k[u] * 16) = out;
+                    }
+            }
+        }
+    }
+}
+
 template <int H_>   // 0: run-time head count
 __device__ __forceinline__ void rows_rider(const RowsJob& jb, unsigned int wg, unsigned int n_wgs) {
+    if (jb.in == HEPT_IN_BF16) return rows_rider16<H_, HEPT_IN_BF16>(jb, wg, n_wgs);
+    if (jb.in == HEPT_IN_F16) return rows_rider16<H_, HEPT_IN_F16>(jb, wg, n_wgs);
+    const float* v32 = reinterpret_cast<const float*>(jb.v);
     // A wave takes a tile of 8 consecutive points (one contiguous run of v) at a time.  A row half is PPR 16-B pieces
     // (4 of 8 bf16 values, or 8 of 4 floats); lane order inside the tile is [head][point][piece]: a store instruction
     // writes whole 64-B / 128-B row halves of consecutive points of one head -- the pattern of the row builder's
@@ -463,7 +541,7 @@ __device__ __forceinline__ void rows_rider(const RowsJob& jb, unsigned int wg, u
                     n[u] = n0 + ((i / PPR) & 7u);
                     hd[u] = i / (8 * PPR);
                     const bool data = hd[u] < H && n[u] < (unsigned int)jb.raw_size && 4 * k[u] < D;
-                    x[u] = data ? hept_ld<HEPT_NT_RIDER_IN32>(reinterpret_cast<const f32x4*>(jb.v + (size_t)n[u] * HD + hd[u] * D + 4 * k[u]))
+                    x[u] = data ? hept_ld<HEPT_NT_RIDER_IN32>(reinterpret_cast<const f32x4*>(v32 + (size_t)n[u] * HD + hd[u] * D + 4 * k[u]))
                                 : f32x4{4 * k[u] == D ? 1.f : 0.f, 0.f, 0.f, 0.f};
                 }
 #pragma unroll
@@ -486,7 +564,7 @@ __device__ __forceinline__ void rows_rider(const RowsJob& jb, unsigned int wg, u
                     n[u] = n0 + ((i / PPR) & 7u);
                     hd[u] = i / (8 * PPR);
                     const bool row = hd[u] < H && n[u] < (unsigned int)jb.raw_size;
-                    const float* src = jb.v + (size_t)n[u] * HD + hd[u] * D + 8 * k[u];
+                    const float* src = v32 + (size_t)n[u] * HD + hd[u] * D + 8 * k[u];
                     x[u][0] = (row && 8 * k[u] < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const f32x4*>(src)) : f32x4{0.f, 0.f, 0.f, 0.f};
                     x[u][1] = (row && 8 * k[u] + 4 < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const f32x4*>(src + 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
                     // the 1.0 of column D (D % 4 == 0: the first element of one of the two quads)
@@ -1400,6 +1478,7 @@ RowsJob rows_job(const HeptRowsJob* r) {
     jb.f32 = (r->precision == HEPT_PREC_F32 || r->precision == HEPT_PREC_F32_MFMA || r->precision == HEPT_PREC_F32_DIFF) ? 1 : 0;
     static const int vy = [] { const char* e = getenv("HEPT_ROW_RIDERS"); const int n = e ? atoi(e) : 0; return n > 0 && n <= 64 ? n : HEPT_ROWS_RIDERS; }();
     jb.vy = vy;   // (HEPT_ROW_RIDERS=<grid rows>: tuning; read once)
+    jb.in = r->in_dtype;
     return jb;
 }
 
@@ -1430,6 +1509,12 @@ bool hept_sort_carries_rows(int N, int H, int D) {
     return N > SMALL_CAP && (size_t)N <= (size_t)NTOP * (BKT_CAP_SMALL / 2) && D >= 4 && D % 4 == 0 && D <= 28 && H >= 1;
 }
 
+// 16-bit v rows reach the riders as 8-byte pieces
+static inline bool rows_in_ok(const HeptRowsJob* r) {
+    if (r->in_dtype == HEPT_IN_F32) return true;
+    return (r->in_dtype == HEPT_IN_BF16 || r->in_dtype == HEPT_IN_F16) && (reinterpret_cast<uintptr_t>(r->v) & 7) == 0;
+}
+
 extern "C" int hept_sort_tables(const float* qproj, const float* kproj, const int64_t* codes, const float* minmax,
                                 int N, int H, int T, int t0, int Tl, void* sort_ws, int32_t* qpos, int32_t* kpos,
                                 void* stream) {
@@ -1441,7 +1526,7 @@ int hept_sort_tables_rows(const float* qproj, const float* kproj, const int64_t*
                           int T, int t0, int Tl, void* sort_ws, int32_t* qpos, int32_t* kpos, const HeptRowsJob* rows,
                           void* stream, bool zeroed) {
     if (!qproj || !kproj || !codes || !minmax || !sort_ws || !qpos || !kpos) return HEPT_ERR_ARG;
-    if (rows && (!rows->v || !rows->kvhat || rows->N != N || !hept_sort_carries_rows(N, rows->H, rows->D))) return HEPT_ERR_ARG;
+    if (rows && (!rows->v || !rows->kvhat || rows->N != N || !hept_sort_carries_rows(N, rows->H, rows->D) || !rows_in_ok(rows))) return HEPT_ERR_ARG;
     if (N < 1 || H < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
     if (kpos != qpos + (size_t)Tl * H * N) return HEPT_ERR_ARG;  // one (2,Tl,H,N) array: q then k
     hipStream_t st = (hipStream_t)stream;
@@ -1466,7 +1551,7 @@ int hept_sort_tables_src_rows(const float* qproj, const float* kproj, const floa
                               int32_t* qpos, int32_t* kpos, const HeptRowsJob* rows, void* stream, bool zeroed) {
     if (!qproj || !kproj || !eta_idx || !phi_idx || !cfac || !minmax || !sort_ws || !qpos || !kpos)
         return HEPT_ERR_ARG;
-    if (rows && (!rows->v || !rows->kvhat || rows->N != N || !hept_sort_carries_rows(N, rows->H, rows->D))) return HEPT_ERR_ARG;
+    if (rows && (!rows->v || !rows->kvhat || rows->N != N || !hept_sort_carries_rows(N, rows->H, rows->D) || !rows_in_ok(rows))) return HEPT_ERR_ARG;
     if (N < 1 || H < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
     if (kpos != qpos + (size_t)Tl * H * N) return HEPT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;

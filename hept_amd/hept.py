@@ -162,9 +162,15 @@ class HEPTAttention(nn.Module):
             # (w_rpe.weight goes to the C call as it is: sqrt_w (H, C), reference example/hept.py:22-25, is computed in
             #  the row builder's prologue on every forward -- nothing derived from a parameter is cached here)
             f32 = torch.float32
-            q2 = query if (query.dtype is f32 and query.dim() == 2) else query.reshape(n, h * d).float()
-            k2 = key if (key.dtype is f32 and key.dim() == 2) else key.reshape(n, h * d).float()
-            v2 = value if (value.dtype is f32 and value.dim() == 2) else value.reshape(n, h * d).float()
+            if (self.sharding is None and query.dtype in (torch.bfloat16, torch.float16)
+                    and key.dtype is query.dtype and value.dtype is query.dtype):
+                # the usual dtypes under torch.autocast: the row builder reads 16-bit rows itself and widens them in
+                # registers (exact), so no float32 copies are made; reshape of a contiguous (N, H, D) is a view
+                q2, k2, v2 = [x if x.dim() == 2 else x.reshape(n, h * d) for x in (query, key, value)]
+            else:   # mixed dtypes, table sharding (f32 entry points): widen here
+                q2 = query if (query.dtype is f32 and query.dim() == 2) else query.reshape(n, h * d).float()
+                k2 = key if (key.dtype is f32 and key.dim() == 2) else key.reshape(n, h * d).float()
+                v2 = value if (value.dtype is f32 and value.dim() == 2) else value.reshape(n, h * d).float()
             if self.sharding is None and torch.compiler.is_compiling():
                 # one opaque graph node instead of a ctypes call Dynamo cannot trace (hept_amd/library.py)
                 from .library import forward_op, forward_src_op

@@ -5,7 +5,8 @@ The reference model is run under ``torch.compile(model)`` in its example noteboo
 ``libhept_hip.so``; registered as opaque custom ops with shape-only "fake" kernels the whole
 operator becomes ONE node of the captured graph instead of a graph break.  ``HEPTAttention.forward``
 routes through these ops only while a compiler is tracing; eager calls keep the direct path.
-There is no CPU kernel behind any of them.
+There is no CPU kernel behind any of them.  ``q``, ``k``, ``v`` of ``forward`` / ``forward_src`` may be float32,
+bfloat16 or float16 (one dtype for the three): they reach ``ops`` un-widened, and the result is float32 either way.
 """
 from __future__ import annotations
 

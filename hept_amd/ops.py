@@ -84,6 +84,34 @@ def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.clone() if t.data_ptr() % 16 else t
 
 
+# element types the *_in entry points read natively (include/hept_hip.h: HEPT_IN_*)
+_IN_CODE = {torch.float32: _lib.IN_F32, torch.bfloat16: _lib.IN_BF16, torch.float16: _lib.IN_F16}
+IN_F32, IN_BF16, IN_F16 = _lib.IN_F32, _lib.IN_BF16, _lib.IN_F16
+
+
+def _inc(t: torch.Tensor, name: str) -> torch.Tensor:
+    """``_f32c`` for query / key / value, which may also be bfloat16 or float16: the row builder widens 16-bit rows in
+    registers (every such value is a float32 value), so no float32 copy is made."""
+    if t.dtype in _IN_CODE and t.is_cuda and t.is_contiguous() and not (t.data_ptr() & 15):
+        return t
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (hept_amd has no CPU path); got device {t.device}")
+    if t.dtype not in _IN_CODE:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    t = t.contiguous()
+    # (the tuned row builder fetches 16-byte pieces of 16-bit rows as well: the same repair as _f32c)
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _qkv_in(q, k, v):
+    """query, key, value as the C ABI takes them and their common HEPT_IN_* code; the three must share one dtype."""
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError(f"query, key and value must share one dtype (float32, bfloat16 or float16), got "
+                        f"{q.dtype}, {k.dtype} and {v.dtype}")
+    q, k, v = _inc(q, "query"), _inc(k, "key"), _inc(v, "value")
+    return q, k, v, _IN_CODE[q.dtype]
+
+
 def _dims(q: torch.Tensor, coords: torch.Tensor, alpha: torch.Tensor) -> Tuple[int, int, int, int, int]:
     n, hd = q.shape
     h, e, t = alpha.shape
@@ -147,9 +175,8 @@ def prep_hash(q, k, v, coords, sqrt_w, alpha, codes, precision="fp32", t0: int =
     """``rows`` = (qhat, kvhat) of an earlier call with the same inputs and precision: the row buffers are reused
     (callers that walk more than HEPT_MAX_TABLES tables in chunks rebuild identical rows for every chunk)."""
     lib = _lib.load()
-    q, k, v, coords, sqrt_w, alpha = (_f32c(x, nm) for x, nm in
-                                      ((q, "query"), (k, "key"), (v, "value"), (coords, "coords"),
-                                       (sqrt_w, "sqrt_w"), (alpha, "alpha")))
+    q, k, v, in_code = _qkv_in(q, k, v)
+    coords, sqrt_w, alpha = (_f32c(x, nm) for x, nm in ((coords, "coords"), (sqrt_w, "sqrt_w"), (alpha, "alpha")))
     n, h, d, c, t = _dims(q, coords, alpha)
     if tuple(sqrt_w.shape) != (h, c):   # the kernel indexes it as (H, C): a mismatch would be an out-of-bounds read
         raise ValueError(f"sqrt_w must have shape {(h, c)}, got {tuple(sqrt_w.shape)}")
@@ -174,10 +201,10 @@ def prep_hash(q, k, v, coords, sqrt_w, alpha, codes, precision="fp32", t0: int =
     qproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
     kproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
     minmax = torch.empty(tl, h, _lib.PREP_GRID, 4, device=dev, dtype=torch.float32)
-    _lib.check(lib.hept_prep_hash(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), sqrt_w.data_ptr(),
-                                  alpha.data_ptr(), codes.data_ptr() if codes is not None else None, n, raw_size, h, d, c,
-                                  t, t0, tl, prec, qhat.data_ptr(), kvhat.data_ptr(),
-                                  qproj.data_ptr(), kproj.data_ptr(), minmax.data_ptr(), _stream(q)),
+    _lib.check(lib.hept_prep_hash_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), in_code, coords.data_ptr(),
+                                     sqrt_w.data_ptr(), alpha.data_ptr(), codes.data_ptr() if codes is not None else None,
+                                     n, raw_size, h, d, c, t, t0, tl, prec, qhat.data_ptr(), kvhat.data_ptr(),
+                                     qproj.data_ptr(), kproj.data_ptr(), minmax.data_ptr(), _stream(q)),
                "hept_prep_hash")
     return dict(qhat=qhat, kvhat=kvhat, qproj=qproj, kproj=kproj, minmax=minmax)
 
@@ -385,10 +412,15 @@ def geo_args(region_indices, regions_h, n_tables: int, n_heads: int, n: int):
     return eta, phi, cfac
 
 
-def _prepare(q, k, v, coords, codes, w_rpe_weight, alpha, block_size, w_per_dist):
-    q, k, v, coords, w, alpha = (_f32c(x, nm) for x, nm in
-                                 ((q, "query"), (k, "key"), (v, "value"), (coords, "coords"),
-                                  (w_rpe_weight, "w_rpe.weight"), (alpha, "e2lsh.alpha")))
+def _prepare(q, k, v, coords, codes, w_rpe_weight, alpha, block_size, w_per_dist, in16: bool = False):
+    """``in16``: the caller's entry point reads bfloat16 / float16 query, key, value natively (``_qkv_in``); the others
+    (table sharding) take float32 only."""
+    if in16:
+        q, k, v, _ = _qkv_in(q, k, v)
+    else:
+        q, k, v = (_f32c(x, nm) for x, nm in ((q, "query"), (k, "key"), (v, "value")))
+    coords, w, alpha = (_f32c(x, nm) for x, nm in
+                        ((coords, "coords"), (w_rpe_weight, "w_rpe.weight"), (alpha, "e2lsh.alpha")))
     n, h, d, c, t = _dims(q, coords, alpha)
     if k.shape != q.shape or v.shape != q.shape or coords.shape[0] != n:
         raise ValueError("query, key, value and coords must agree on the number of points")
@@ -410,7 +442,7 @@ def forward(q, k, v, coords, codes, w_rpe_weight, alpha, out_weight, out_bias, *
     """Whole operator (reference ``example/hept.py:43-81``) in one C call; returns (N, D) float32."""
     lib = _lib.load()
     q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
-                                                                block_size, w_per_dist)
+                                                                block_size, w_per_dist, in16=True)
     prec = precision_code(precision)
     _lib.check(_check_shape_cached(n, h, d, c, t, block_size), "hept_check_shape")
     need = _workspace_bytes_cached(n, h, d, c, t, block_size, prec)
@@ -419,10 +451,11 @@ def forward(q, k, v, coords, codes, w_rpe_weight, alpha, out_weight, out_bias, *
     ow = _f32c(out_weight, "out_linear.weight")
     ob = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
     out = torch.empty(n, d, device=q.device, dtype=torch.float32)
-    _lib.check(lib.hept_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), codes.data_ptr(),
-                                w.data_ptr(), alpha.data_ptr(), ow.data_ptr(), ob.data_ptr() if ob is not None else None,
-                                n, h, d, c, w_per_dist, t, block_size, prec, workspace.data_ptr(), workspace.numel(),
-                                out.data_ptr(), stream if stream is not None else _stream(q)), "hept_forward")
+    _lib.check(lib.hept_forward_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(),
+                                   codes.data_ptr(), w.data_ptr(), alpha.data_ptr(), ow.data_ptr(),
+                                   ob.data_ptr() if ob is not None else None, n, h, d, c, w_per_dist, t, block_size, prec,
+                                   workspace.data_ptr(), workspace.numel(), out.data_ptr(),
+                                   stream if stream is not None else _stream(q)), "hept_forward")
     return out
 
 
@@ -443,17 +476,18 @@ def forward_partial(q, k, v, coords, codes, w_rpe_weight, alpha, *, block_size: 
     the same sum as packed rows (N, H, 16) int32 (needs ``packed_partials(precision, D)``)."""
     lib = _lib.load()
     q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
-                                                                block_size, w_per_dist)
+                                                                block_size, w_per_dist, in16=True)
     prec = precision_code(precision)
     _lib.check(lib.hept_check_shape(n, h, d, c, tl, block_size), "hept_check_shape")
     need = int(lib.hept_workspace_bytes(n, h, d, c, tl, block_size, prec))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
     acc = _acc_buffer(n, h, packed, q.device)
-    _lib.check(lib.hept_forward_partial(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), codes.data_ptr(),
-                                        w.data_ptr(), alpha.data_ptr(), n, h, d, c, w_per_dist, t, t0, tl, block_size,
-                                        prec, PREC_BF16 if packed else PREC_F32, workspace.data_ptr(),
-                                        workspace.numel(), acc.data_ptr(), _stream(q)), "hept_forward_partial")
+    _lib.check(lib.hept_forward_partial_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(),
+                                           codes.data_ptr(), w.data_ptr(), alpha.data_ptr(), n, h, d, c, w_per_dist, t,
+                                           t0, tl, block_size, prec, PREC_BF16 if packed else PREC_F32,
+                                           workspace.data_ptr(), workspace.numel(), acc.data_ptr(), _stream(q)),
+               "hept_forward_partial")
     return acc
 
 
@@ -464,7 +498,7 @@ def forward_src(q, k, v, coords, region_indices, regions_h, raw_size: int, w_rpe
     """Whole operator of the reference's src variant (``src/models/attention/hept.py:74-117``); (N, D) float32."""
     lib = _lib.load()
     q, k, v, coords, _, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, None, w_rpe_weight, alpha, block_size,
-                                                             w_per_dist)
+                                                             w_per_dist, in16=True)
     eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
     prec = precision_code(precision)
     _lib.check(lib.hept_check_shape(n, h, d, c, t, block_size), "hept_check_shape")
@@ -474,11 +508,11 @@ def forward_src(q, k, v, coords, region_indices, regions_h, raw_size: int, w_rpe
     ow = _f32c(out_weight, "out_linear.weight")
     ob = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
     out = torch.empty(n, d, device=q.device, dtype=torch.float32)
-    _lib.check(lib.hept_forward_src(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), eta.data_ptr(),
-                                    phi.data_ptr(), cfac.data_ptr(), int(raw_size), w.data_ptr(), alpha.data_ptr(),
-                                    ow.data_ptr(), ob.data_ptr() if ob is not None else None, n, h, d, c, w_per_dist,
-                                    t, block_size, prec, workspace.data_ptr(), workspace.numel(), out.data_ptr(),
-                                    _stream(q)), "hept_forward_src")
+    _lib.check(lib.hept_forward_src_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(),
+                                       eta.data_ptr(), phi.data_ptr(), cfac.data_ptr(), int(raw_size), w.data_ptr(),
+                                       alpha.data_ptr(), ow.data_ptr(), ob.data_ptr() if ob is not None else None, n, h,
+                                       d, c, w_per_dist, t, block_size, prec, workspace.data_ptr(), workspace.numel(),
+                                       out.data_ptr(), _stream(q)), "hept_forward_src")
     return out
 
 
@@ -489,7 +523,7 @@ def forward_partial_src(q, k, v, coords, region_indices, regions_h, raw_size: in
     """src variant, tables [t0, t0+tl) only: acc (N, H, 32) = sum over those tables of [numer | denom]."""
     lib = _lib.load()
     q, k, v, coords, _, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, None, w_rpe_weight, alpha, block_size,
-                                                             w_per_dist)
+                                                             w_per_dist, in16=True)
     eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
     prec = precision_code(precision)
     _lib.check(lib.hept_check_shape(n, h, d, c, tl, block_size), "hept_check_shape")
@@ -497,11 +531,11 @@ def forward_partial_src(q, k, v, coords, region_indices, regions_h, raw_size: in
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
     acc = _acc_buffer(n, h, packed, q.device)
-    _lib.check(lib.hept_forward_partial_src(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(),
-                                            eta.data_ptr(), phi.data_ptr(), cfac.data_ptr(), int(raw_size),
-                                            w.data_ptr(), alpha.data_ptr(), n, h, d, c, w_per_dist, t, t0, tl,
-                                            block_size, prec, PREC_BF16 if packed else PREC_F32,
-                                            workspace.data_ptr(), workspace.numel(), acc.data_ptr(), _stream(q)),
+    _lib.check(lib.hept_forward_partial_src_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype],
+                                               coords.data_ptr(), eta.data_ptr(), phi.data_ptr(), cfac.data_ptr(),
+                                               int(raw_size), w.data_ptr(), alpha.data_ptr(), n, h, d, c, w_per_dist, t,
+                                               t0, tl, block_size, prec, PREC_BF16 if packed else PREC_F32,
+                                               workspace.data_ptr(), workspace.numel(), acc.data_ptr(), _stream(q)),
                "hept_forward_partial_src")
     return acc
 

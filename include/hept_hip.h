@@ -14,7 +14,7 @@
  * handled by this call (table sharding: tables [t0, t0+Tl) of T).
  *
  * Device layouts (all row-major, contiguous):
- *   q,k,v        (N, H*D)   f32      inputs
+ *   q,k,v        (N, H*D)   f32      inputs (the *_in entry points also take bf16 or fp16: HEPT_IN_*)
  *   coords       (N, C)     f32
  *   w_rpe        (H*D, (C-1)*K) f32  the nn.Linear weight of the caller's w_rpe
  *   alpha        (H, E, T)  f32      E2LSH projection
@@ -64,6 +64,13 @@ extern "C" {
                                 q^.k^ - |q^|^2/2 - |k^|^2/2: no cancellation when sqrt_w . coords is large (a trained
                                 w_rpe on un-normalised coordinates: terms of ~3e8 whose f32 sum is noise).  The mode for
                                 such inputs; mathematically the same operator (example/hept.py:8-12) */
+
+/* Element type of q, k and v (one type for all three) at the *_in entry points.  Every bf16 and every fp16 value is an
+ * f32 value: the row builder and the v-row riders widen the 16-bit rows in registers and run the same arithmetic, so
+ * the results are bit-identical to the f32 entry points called on the widened tensors. */
+#define HEPT_IN_F32 0
+#define HEPT_IN_BF16 1
+#define HEPT_IN_F16 2
 
 #define HEPT_ROW 32          /* padded row width (elements) of qhat / k / v / part rows */
 #define HEPT_MAX_TABLES 8    /* tables per hept_prep_hash / hept_sort_tables call; the whole-operator entry points
@@ -185,6 +192,38 @@ int hept_forward_partial(const float* q, const float* k, const float* v, const f
                          int N, int H, int D, int C, int K, int T, int t0, int Tl, int B,
                          int precision, int acc_precision, void* workspace, size_t workspace_bytes,
                          float* acc, void* stream);
+
+/* The same calls (and the stage entry hept_prep_hash, all three roles) on q, k, v of element type `in_dtype`
+ * (HEPT_IN_*; HEPT_IN_F32 is exactly the entry point without the suffix).  16-bit q, k, v are contiguous (N, H*D);
+ * their base is 16-byte aligned on the shapes that take the tuned row builder (H == 8 with the shipped (D, C) pairs:
+ * a tile of 8 points is fetched as 16-byte pieces of 8 elements) and 2-byte aligned on every other shape;
+ * HEPT_ERR_ARG otherwise, and for an unknown in_dtype.  The sharded calls, hept_partial_begin* and the Attn block take
+ * f32 only. */
+int hept_prep_hash_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                      const float* sqrt_w, const float* alpha, const int64_t* codes,
+                      int N, int raw_size, int H, int D, int C, int T, int t0, int Tl, int precision,
+                      void* qhat, void* kvhat, float* qproj, float* kproj, float* minmax, void* stream);
+int hept_forward_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                    const int64_t* codes, const float* w_rpe, const float* alpha,
+                    const float* out_weight, const float* out_bias,
+                    int N, int H, int D, int C, int K, int T, int B, int precision,
+                    void* workspace, size_t workspace_bytes, float* out, void* stream);
+int hept_forward_partial_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                            const int64_t* codes, const float* w_rpe, const float* alpha,
+                            int N, int H, int D, int C, int K, int T, int t0, int Tl, int B,
+                            int precision, int acc_precision, void* workspace, size_t workspace_bytes,
+                            float* acc, void* stream);
+int hept_forward_src_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                        const float* eta_idx, const float* phi_idx, const float* cfac, int raw_size,
+                        const float* w_rpe, const float* alpha, const float* out_weight, const float* out_bias,
+                        int N, int H, int D, int C, int K, int T, int B, int precision,
+                        void* workspace, size_t workspace_bytes, float* out, void* stream);
+int hept_forward_partial_src_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
+                                const float* eta_idx, const float* phi_idx, const float* cfac, int raw_size,
+                                const float* w_rpe, const float* alpha,
+                                int N, int H, int D, int C, int K, int T, int t0, int Tl, int B,
+                                int precision, int acc_precision, void* workspace, size_t workspace_bytes,
+                                float* acc, void* stream);
 
 /* Table sharding with the exchange pipelined behind the block attention: hept_partial_begin runs
  * everything up to the sort for tables [t0, t0+Tl) and leaves rows and permutations in `workspace`
