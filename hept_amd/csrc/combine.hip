@@ -954,7 +954,8 @@ int combine_launch(hipStream_t st, const float* part, int Tl, int N, int H, int 
 extern "C" int hept_combine_groups(const float* part, int part_precision, int Tl, int N, int H, int D, int n0,
                                    int n_count, int HG, size_t group_stride, const float* out_weight,
                                    const float* out_bias, float* out, void* stream) {
-    if (!part || !out_weight || !out) return HEPT_ERR_ARG;
+    // (an empty point slice -- a rank of a sharded world beyond the last point -- has no output buffer to speak of)
+    if (!part || !out_weight || (!out && n_count != 0)) return HEPT_ERR_ARG;
     if (Tl < 1 || N < 1 || H < 1 || H > 16 || D < 1 || D > 27 || n0 < 0 || n_count < 0 || n0 + n_count > N)
         return HEPT_ERR_SHAPE;
     if (HG < 1 || HG > H || H % HG != 0) return HEPT_ERR_SHAPE;

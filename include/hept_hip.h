@@ -160,6 +160,8 @@ int hept_reduce_heads(const float* part, int part_precision, int Tl, int N, int 
 /* replaces the cross-table combine (example/hept.py:79) and out_linear (:80) for points
  * [n0, n0+n_count): out[n] = bias + W . (sum_t numer / sum_t denom).  `part` may hold Tl >= 1
  * tables (Tl == 1: an already reduced `acc`).  out points at row n0 of the (N, D) output.
+ * n_count == 0 (an empty point slice: a rank beyond the last point) launches nothing and returns HEPT_OK; `out` may
+ * then be null.  The same holds for hept_combine_groups.
  * D == 24: `part` and `out_weight` must be 16-byte aligned (rows and weight columns are read as 16-B pieces);
  * HEPT_ERR_ARG otherwise. */
 int hept_combine_out(const float* part, int part_precision, int Tl, int N, int H, int D, int n0,
