@@ -61,6 +61,8 @@ SIGNATURES = {
     "hept_combine_ffn": (c_int, [_P] + [c_int] * 7 + [_P] * 5 + [c_float] + [_P] * 6),
     "hept_attn_block_forward": (c_int, [_P] * 4 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
     "hept_attn_block_forward_src": (c_int, [_P] * 5 + [c_int, _P] + [c_int] * 8 + [_P, c_size_t, _P, _P]),
+    "hept_attn_stack_forward": (c_int, [_P, c_int] + [_P] * 3 + [c_int] * 9 + [_P, c_size_t, _P]),
+    "hept_attn_stack_forward_src": (c_int, [_P, c_int] + [_P] * 4 + [c_int, _P] + [c_int] * 9 + [_P, c_size_t, _P]),
     "hept_combine_bwd_scratch_bytes": (c_size_t, [c_int]),
     "hept_combine_bwd_scratch_bytes_shape": (c_size_t, [c_int] * 3),
     "hept_combine_bwd": (c_int, [_P] * 3 + [c_int] * 3 + [_P] * 4 + [c_size_t, _P]),

@@ -61,6 +61,21 @@ class Attn(nn.Module):
         return (x.is_cuda and not self.training and not torch.is_grad_enabled() and self.dim_per_head == 24
                 and self.num_heads == 8 and coords_dim in (2, 4, 6) and self.attn.sharding is None)
 
+    def _block_params(self):
+        """The block's tensors under the reference's state-dict names, as ``ops.attn_block_forward`` takes them."""
+        a = self.attn
+        return {
+            "norm1.weight": self.norm1.weight, "norm1.bias": self.norm1.bias, "w_q.weight": self.w_q.weight,
+            "w_k.weight": self.w_k.weight, "w_v.weight": self.w_v.weight,
+            # the weight itself: sqrt_w (H, C) is computed inside the row builder on every call (no cached copy that an
+            # in-place update of the parameter could leave stale)
+            "w_rpe.weight": self.w_rpe.weight,
+            "attn.e2lsh.alpha": a.e2lsh.alpha, "attn.out_linear.weight": a.out_linear.weight,
+            "attn.out_linear.bias": a.out_linear.bias, "norm2.weight": self.norm2.weight,
+            "norm2.bias": self.norm2.bias, "ff.0.weight": self.ff[0].weight, "ff.0.bias": self.ff[0].bias,
+            "ff.2.weight": self.ff[2].weight, "ff.2.bias": self.ff[2].bias,
+        }
+
     # training / grad-enabled calls: LayerNorm + projections + operator as one autograd node (False: compose modules)
     fuse_training = True
 
@@ -115,17 +130,7 @@ class Attn(nn.Module):
         ws = self._workspace
         if ws is None or ws.numel() < need or ws.device != x.device:
             ws = self._workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
-        params = {
-            "norm1.weight": self.norm1.weight, "norm1.bias": self.norm1.bias, "w_q.weight": self.w_q.weight,
-            "w_k.weight": self.w_k.weight, "w_v.weight": self.w_v.weight,
-            # the weight itself: sqrt_w (H, C) is computed inside the row builder on every call (no cached copy that an
-            # in-place update of the parameter could leave stale)
-            "w_rpe.weight": self.w_rpe.weight,
-            "attn.e2lsh.alpha": a.e2lsh.alpha, "attn.out_linear.weight": a.out_linear.weight,
-            "attn.out_linear.bias": a.out_linear.bias, "norm2.weight": self.norm2.weight,
-            "norm2.bias": self.norm2.bias, "ff.0.weight": self.ff[0].weight, "ff.0.bias": self.ff[0].bias,
-            "ff.2.weight": self.ff[2].weight, "ff.2.bias": self.ff[2].bias,
-        }
+        params = self._block_params()
         common = dict(num_heads=self.num_heads, block_size=a.block_size, w_per_dist=a.num_w_per_dist,
                       eps1=self.norm1.eps, eps2=self.norm2.eps, precision=a.precision, workspace=ws)
         if src:

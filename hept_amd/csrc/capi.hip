@@ -671,17 +671,26 @@ extern "C" int hept_forward_sharded_src(hept_comm* comm, const float* q, const f
 }
 
 namespace {
-// the whole Attn block for either variant: geo.eta == nullptr takes the example variant's AND codes, else the src
-// variant's region shift and padding rows (rows >= geo.raw_size: zero q^, k^, v, hash +inf; the residual and the
-// feed-forward still run on them, as in the reference's block)
-int attn_block_impl(const float* x, const float* coords, const int64_t* codes, const GeoShift& geo,
-                    const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B, int precision,
-                    void* workspace, size_t workspace_bytes, float* y, void* stream) {
-    if (!x || !coords || !p || !workspace || !y) return HEPT_ERR_ARG;
+// refusals of one block that need no HIP call (the stack entry runs them for every layer before it launches anything)
+int attn_params_check(const hept_attn_params* p) {
+    if (!p) return HEPT_ERR_ARG;
     if (!p->norm1_w || !p->norm1_b || !p->w_q || !p->w_k || !p->w_v || !p->w_rpe || !p->alpha || !p->out_w ||
         !p->norm2_w || !p->norm2_b || !p->ff1_w || !p->ff1_b || !p->ff2_w || !p->ff2_b)
         return HEPT_ERR_ARG;
-    int rc = hept_check_shape(N, H, D, C, T, B);
+    return HEPT_OK;
+}
+
+// the whole Attn block for either variant: geo.eta == nullptr takes the example variant's AND codes, else the src
+// variant's region shift and padding rows (rows >= geo.raw_size: zero q^, k^, v, hash +inf; the residual and the
+// feed-forward still run on them, as in the reference's block).
+// ldx / ldy: row pitches of x and y in floats (D, D: the contiguous (N, D) tensors of hept_attn_block_forward).
+int attn_block_impl(const float* x, int ldx, const float* coords, const int64_t* codes, const GeoShift& geo,
+                    const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B, int precision,
+                    void* workspace, size_t workspace_bytes, float* y, int ldy, void* stream) {
+    if (!x || !coords || !p || !workspace || !y) return HEPT_ERR_ARG;
+    int rc = attn_params_check(p);
+    if (rc) return rc;
+    rc = hept_check_shape(N, H, D, C, T, B);
     if (rc) return rc;
     if (D != 24) return HEPT_ERR_SHAPE;
     const Workspace w = carve(workspace, N, H, C, T, precision);
@@ -699,7 +708,7 @@ int attn_block_impl(const float* x, const float* coords, const int64_t* codes, c
         void* zptr = nullptr;
         size_t zbytes = 0;
         hept_sort_zero_block(w.sort_ws, N, H, tc, &zptr, &zbytes);   // (see run_begin)
-        rc = hept_prep_hash_fused_rpe(x, p->norm1_w, p->norm1_b, p->eps1, p->w_q, p->w_k, p->w_v, coords, p->w_rpe, K,
+        rc = hept_prep_hash_fused_rpe(x, ldx, p->norm1_w, p->norm1_b, p->eps1, p->w_q, p->w_k, p->w_v, coords, p->w_rpe, K,
                                       p->alpha, codes, N, raw_size, H, D, C, T, c0, tc, precision, w.qhat, w.kvhat, w.qproj,
                                       w.kproj, w.minmax, stream, zptr, zbytes);
         if (rc) return rc;
@@ -723,11 +732,39 @@ int attn_block_impl(const float* x, const float* coords, const int64_t* codes, c
     rc = hept_block_attn(w.qhat, w.kvhat, qpos, kpos, N, H, D, T, B, precision, w.part, stream);
     if (rc) return rc;
     prof_mark(3, st);
-    rc = hept_combine_ffn(w.part, hept_part_precision(precision, D), T, N, H, D, 0, N, p->out_w, p->out_b, x,
-                          p->norm2_w, p->norm2_b, p->eps2, p->ff1_w, p->ff1_b, p->ff2_w, p->ff2_b, y, stream);
+    rc = hept_combine_ffn_ld(w.part, hept_part_precision(precision, D), T, N, H, D, 0, N, p->out_w, p->out_b, x, ldx,
+                             p->norm2_w, p->norm2_b, p->eps2, p->ff1_w, p->ff1_b, p->ff2_w, p->ff2_b, y, ldy, stream);
     prof_mark(4, st);
     prof_call_done();
     return rc;
+}
+
+// L blocks in a row on one (N, ld) buffer and ONE workspace: layer i reads columns [i D, (i+1) D) and writes columns
+// [(i+1) D, (i+2) D) of the same rows.  The layers are stream-ordered, and a block re-initialises everything it reads
+// in the workspace on every call (the sort's zero block, minmax, the rows), so the layers share it as consecutive
+// single-block calls on one module do.  Everything that can be refused is refused before the first HIP call.
+int attn_stack_impl(float* xcat, int ld, const float* coords, const int64_t* codes, const GeoShift& geo,
+                    const hept_attn_params* layers, int L, int N, int H, int D, int C, int K, int T, int B,
+                    int precision, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!xcat || !coords || !layers || !workspace) return HEPT_ERR_ARG;
+    for (int i = 0; i < L; ++i)
+        if (attn_params_check(layers + i)) return HEPT_ERR_ARG;
+    if (L < 1 || D != 24 || (long long)ld < ((long long)L + 1) * D || ld % 4 != 0) return HEPT_ERR_SHAPE;
+    int rc = hept_check_shape(N, H, D, C, T, B);
+    if (rc) return rc;
+    if (geo.eta && (geo.raw_size < 0 || geo.raw_size > N)) return HEPT_ERR_SHAPE;
+    if (K < 0 || (K > 0 && H * (C - 1) * K > 1024)) return HEPT_ERR_SHAPE;
+    // D = 24: every column block starts at a multiple of 96 B, every row at a multiple of 4 ld B -- a 16-B aligned base
+    // keeps all the f32x4 accesses of the row builder and of the combine's epilogue aligned
+    if (reinterpret_cast<uintptr_t>(xcat) & 15) return HEPT_ERR_ARG;
+    if (workspace_bytes < carve(nullptr, N, H, C, T, precision).bytes) return HEPT_ERR_ARG;
+    for (int i = 0; i < L; ++i) {
+        // (each layer is one profiled call, like a single block: stage times per block stay comparable)
+        rc = attn_block_impl(xcat + (size_t)i * D, ld, coords, codes, geo, layers + i, N, H, D, C, K, T, B, precision,
+                             workspace, workspace_bytes, xcat + (size_t)(i + 1) * D, ld, stream);
+        if (rc) return rc;
+    }
+    return HEPT_OK;
 }
 }  // namespace
 
@@ -736,8 +773,8 @@ extern "C" int hept_attn_block_forward(const float* x, const float* coords, cons
                                        int precision, void* workspace, size_t workspace_bytes, float* y,
                                        void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return attn_block_impl(x, coords, codes, GeoShift{}, p, N, H, D, C, K, T, B, precision, workspace, workspace_bytes,
-                           y, stream);
+    return attn_block_impl(x, D, coords, codes, GeoShift{}, p, N, H, D, C, K, T, B, precision, workspace, workspace_bytes,
+                           y, D, stream);
 }
 
 extern "C" int hept_attn_block_forward_src(const float* x, const float* coords, const float* eta_idx,
@@ -747,8 +784,26 @@ extern "C" int hept_attn_block_forward_src(const float* x, const float* coords, 
                                            void* stream) {
     if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
     if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return attn_block_impl(x, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, p, N, H, D, C, K, T, B,
-                           precision, workspace, workspace_bytes, y, stream);
+    return attn_block_impl(x, D, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, p, N, H, D, C, K, T, B,
+                           precision, workspace, workspace_bytes, y, D, stream);
+}
+
+extern "C" int hept_attn_stack_forward(float* xcat, int ld, const float* coords, const int64_t* codes,
+                                       const hept_attn_params* layers, int L, int N, int H, int D, int C, int K, int T,
+                                       int B, int precision, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!codes) return HEPT_ERR_ARG;
+    return attn_stack_impl(xcat, ld, coords, codes, GeoShift{}, layers, L, N, H, D, C, K, T, B, precision, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int hept_attn_stack_forward_src(float* xcat, int ld, const float* coords, const float* eta_idx,
+                                           const float* phi_idx, const float* cfac, int raw_size,
+                                           const hept_attn_params* layers, int L, int N, int H, int D, int C, int K,
+                                           int T, int B, int precision, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
+    return attn_stack_impl(xcat, ld, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, layers, L, N, H, D, C,
+                           K, T, B, precision, workspace, workspace_bytes, stream);
 }
 
 extern "C" int hept_profile_enable(int mode, int max_calls) {

@@ -77,7 +77,7 @@ struct RawRow {
 // aggregated rows goes through a wave-private LDS tile so that lane (point, half) holds a whole row; each half
 // computes 12 hidden and 12 output units (weights are LDS broadcasts), the halves swap hidden units by shuffle.
 struct FfnIn {
-    const float* x;      // (n_count, D) block input rows, row n0 first
+    const float* x;      // (n_count, D) block input rows, row n0 first, at row pitch ldx floats
     const float* ln_w;   // norm2.weight, norm2.bias
     const float* ln_b;
     const float* w1;     // ff.0.weight (D, D), ff.0.bias
@@ -85,6 +85,10 @@ struct FfnIn {
     const float* w2;     // ff.2.weight (D, D), ff.2.bias
     const float* b2;
     float eps;
+    // Row pitches (floats) of x and of the output y; FFN_D for contiguous rows.  An AttnStack layer reads and writes
+    // different column blocks of the SAME rows of one (N, ld) buffer (ldx == ldy == ld): x and y then interleave in
+    // memory but never share a byte, so the __restrict__ on `out` stays valid.  Multiples of 4 (16-B pieces).
+    int ldx, ldy;
 };
 constexpr int FFN_D = 24, FFN_PITCH = 25, FFN_WFLOATS = 2 * FFN_D * FFN_D + 4 * FFN_D;
 
@@ -395,7 +399,7 @@ __global__ __launch_bounds__(CMB_THREADS) void combine_out_kernel(const float* _
                 if (li < FFN_D) stage_s[hept_acc_row(r, hh) * FFN_PITCH + li] = acc[r] + bia;
             // (one wave's LDS accesses execute in order: the tile is complete when the reads below are issued)
             const bool valid = i < n_count;
-            const f32x4* xs = reinterpret_cast<const f32x4*>(ffn.x + (size_t)(valid ? i : n_count - 1) * FFN_D);
+            const f32x4* xs = reinterpret_cast<const f32x4*>(ffn.x + (size_t)(valid ? i : n_count - 1) * ffn.ldx);
             float y1[FFN_D];
 #pragma unroll
             for (int j = 0; j < FFN_D / 4; ++j) {
@@ -444,7 +448,7 @@ __global__ __launch_bounds__(CMB_THREADS) void combine_out_kernel(const float* _
                 yo[uu] = a;
             }
             if (valid) {
-                f32x4* dst = reinterpret_cast<f32x4*>(out + (size_t)i * FFN_D + hh * (FFN_D / 2));
+                f32x4* dst = reinterpret_cast<f32x4*>(out + (size_t)i * ffn.ldy + hh * (FFN_D / 2));
 #pragma unroll
                 for (int c4 = 0; c4 < FFN_D / 8; ++c4) {
                     f32x4 o;
@@ -994,22 +998,36 @@ extern "C" int hept_combine_out(const float* part, int part_precision, int Tl, i
     return hept_combine_groups(part, part_precision, Tl, N, H, D, n0, n_count, H, 0, out_weight, out_bias, out, stream);
 }
 
-extern "C" int hept_combine_ffn(const float* part, int part_precision, int Tl, int N, int H, int D, int n0,
-                                int n_count, const float* out_weight, const float* out_bias, const float* x,
-                                const float* norm_w, const float* norm_b, float eps, const float* ff1_w,
-                                const float* ff1_b, const float* ff2_w, const float* ff2_b, float* y, void* stream) {
+// internal (common.h): hept_combine_ffn with row pitches ldx / ldy (floats) for x and y -- row n of x starts at
+// x + n * ldx.  Multiples of 4 with 16-B aligned bases (the rows move as 16-B pieces); FFN_D, FFN_D is hept_combine_ffn.
+int hept_combine_ffn_ld(const float* part, int part_precision, int Tl, int N, int H, int D, int n0, int n_count,
+                        const float* out_weight, const float* out_bias, const float* x, int ldx, const float* norm_w,
+                        const float* norm_b, float eps, const float* ff1_w, const float* ff1_b, const float* ff2_w,
+                        const float* ff2_b, float* y, int ldy, void* stream) {
     if (!part || !out_weight || !x || !norm_w || !norm_b || !ff1_w || !ff1_b || !ff2_w || !ff2_b || !y)
         return HEPT_ERR_ARG;
     if (Tl < 1 || N < 1 || H < 1 || H > 16 || D != FFN_D || n0 < 0 || n_count < 0 || n0 + n_count > N)
         return HEPT_ERR_SHAPE;
+    if (ldx < FFN_D || ldy < FFN_D || ldx % 4 != 0 || ldy % 4 != 0) return HEPT_ERR_SHAPE;
+    // (contiguous rows keep the contract they had; pitched rows come from the stack entry, which has checked its buffer)
+    if ((ldx != FFN_D || ldy != FFN_D) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
+        return HEPT_ERR_ARG;
     if (n_count == 0) return HEPT_OK;
     hipStream_t st = (hipStream_t)stream;
-    const FfnIn ffn{x, norm_w, norm_b, ff1_w, ff1_b, ff2_w, ff2_b, eps};
+    const FfnIn ffn{x, norm_w, norm_b, ff1_w, ff1_b, ff2_w, ff2_b, eps, ldx, ldy};
     if (part_precision == HEPT_PREC_BF16)
         return combine_launch<true, true, 24>(st, part, Tl, N, H, D, n0, n_count, out_weight, out_bias, y, ffn);
     if (part_precision == HEPT_PREC_F32)
         return combine_launch<false, true, 24>(st, part, Tl, N, H, D, n0, n_count, out_weight, out_bias, y, ffn);
     return HEPT_ERR_SHAPE;
+}
+
+extern "C" int hept_combine_ffn(const float* part, int part_precision, int Tl, int N, int H, int D, int n0,
+                                int n_count, const float* out_weight, const float* out_bias, const float* x,
+                                const float* norm_w, const float* norm_b, float eps, const float* ff1_w,
+                                const float* ff1_b, const float* ff2_w, const float* ff2_b, float* y, void* stream) {
+    return hept_combine_ffn_ld(part, part_precision, Tl, N, H, D, n0, n_count, out_weight, out_bias, x, FFN_D, norm_w,
+                               norm_b, eps, ff1_w, ff1_b, ff2_w, ff2_b, y, FFN_D, stream);
 }
 
 static bool combine_bwd_tuned(int H, int D) { return D == CB_D && H <= 8; }   // the shipped models' rows

@@ -244,11 +244,16 @@ int hept_prep_hash_rpe(const void* q, const void* k, const void* v, const float*
                        void* stream, int roles = 3,   // roles == 2: q and k rows + hashes only (the v rows: HeptRowsJob)
                        void* zero_ptr = nullptr, size_t zero_bytes = 0,   // scratch the launch clears on its way (hept_sort_zero_block)
                        int in_dtype = HEPT_IN_F32);
-int hept_prep_hash_fused_rpe(const float* x, const float* norm_w, const float* norm_b, float eps, const float* w_q,
+int hept_prep_hash_fused_rpe(const float* x, int ldx, const float* norm_w, const float* norm_b, float eps, const float* w_q,
                              const float* w_k, const float* w_v, const float* coords, const float* sqrt_w, int K,
                              const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T,
                              int t0, int Tl, int precision, void* qhat, void* kvhat, float* qproj, float* kproj,
                              float* minmax, void* stream, void* zero_ptr = nullptr, size_t zero_bytes = 0);
+// hept_combine_ffn with row pitches (floats) for x and y (combine.hip)
+int hept_combine_ffn_ld(const float* part, int part_precision, int Tl, int N, int H, int D, int n0, int n_count,
+                        const float* out_weight, const float* out_bias, const float* x, int ldx, const float* norm_w,
+                        const float* norm_b, float eps, const float* ff1_w, const float* ff1_b, const float* ff2_w,
+                        const float* ff2_b, float* y, int ldy, void* stream);
 // The v half of the kvhat rows written by workgroups that ride in the bucket-sort launch (sort_tables.hip) instead of by
 // the row builder's third role: hept_prep_hash_rpe with roles == 2 leaves them out, hept_sort_tables_rows /
 // hept_sort_tables_src_rows with a job description write them.  hept_sort_carries_rows: the sort of N-key segments has

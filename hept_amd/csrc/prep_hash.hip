@@ -160,6 +160,7 @@ struct FusedIn {
     const float* ln_b;   // norm1.bias (D)
     const float* w_s;    // LDS: this role's projection weight, [h][j][d] (transposed) at head pitch FUSED_WPITCH
     float eps;
+    int ldx;             // row pitch of x in floats (D: contiguous rows; a multiple of 4: the rows are read as 16-B pieces)
 };
 constexpr int FUSED_WPITCH = 24 * 24 + 4;  // head pitch = 4 (mod 32) dwords: the 8 heads' 16-B reads hit 8 distinct bank groups
 
@@ -228,7 +229,7 @@ __device__ __forceinline__ void prep_role(const void* __restrict__ x_, const flo
         f32x4 xr[D4];
         if constexpr (FUSED) {
             float xv[D];
-            const f32x4* xs = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x_) + (size_t)(live ? n : n0) * D);
+            const f32x4* xs = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x_) + (size_t)(live ? n : n0) * fin.ldx);
 #pragma unroll
             for (int j = 0; j < D4; ++j) {
                 const f32x4 v4 = xs[j];
@@ -534,7 +535,7 @@ template <int C, int TILE, int TMAX>
 __global__ __launch_bounds__(PREP_THREADS)
 __attribute__((amdgpu_waves_per_eu((TILE != HEPT_PREC_F32 && TMAX == 4) ? (C == 4 ? 3 : 4) : 2, (TILE != HEPT_PREC_F32 && TMAX == 4) ? 4 : 3)))
 void prep_fused_kernel(
-    const float* __restrict__ x, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+    const float* __restrict__ x, int ldx, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
     const float* __restrict__ wq, const float* __restrict__ wk, const float* __restrict__ wv,
     const float* __restrict__ coords, const float* __restrict__ sqrt_w, int K, const float* __restrict__ alpha,
     const int64_t* __restrict__ codes, int N, int raw_size, int T, int t0, int Tl, void* __restrict__ qhat_,
@@ -567,7 +568,7 @@ void prep_fused_kernel(
             for (int i = threadIdx.x; i < H * C; i += PREP_THREADS) sw_s[i] = sqrt_w[i];
     }
     __syncthreads();
-    const FusedIn fin{ln_w, ln_b, w_s, eps};
+    const FusedIn fin{ln_w, ln_b, w_s, eps, ldx};
     if (role == 0)
         prep_role<D, C, TILE, 0, TMAX, true>(x, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(qhat_),
                                        qproj, red_s, tile_s, minmax, blockIdx.x, cmax_s, fin);
@@ -580,15 +581,15 @@ void prep_fused_kernel(
 }
 
 template <int C>
-int launch_prep_fused(const float* x, const float* ln_w, const float* ln_b, float eps, const float* wq, const float* wk,
+int launch_prep_fused(const float* x, int ldx, const float* ln_w, const float* ln_b, float eps, const float* wq, const float* wk,
                       const float* wv, const float* coords, const float* sqrt_w, int K, const float* alpha,
                       const int64_t* codes, int N, int raw_size, int T, int t0, int Tl, int precision, void* qhat,
                       void* kvhat, float* qproj, float* kproj, float* minmax, hipStream_t st, ZeroJob zero) {
     const dim3 grid(prep_wgs(N), 3);
     // table slots of the kernel (accumulators, alpha slab): 4 for the usual 1-4 tables per call, else HEPT_MAX_TABLES
 #define HEPT_FUSED_LAUNCH(TILE, TMAX)                                                                                  \
-    hipLaunchKernelGGL((prep_fused_kernel<C, TILE, TMAX>), grid, dim3(PREP_THREADS), 0, st, x, ln_w, ln_b, eps, wq, wk, \
-                       wv, coords, sqrt_w, K, alpha, codes, N, raw_size, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero)
+    hipLaunchKernelGGL((prep_fused_kernel<C, TILE, TMAX>), grid, dim3(PREP_THREADS), 0, st, x, ldx, ln_w, ln_b, eps, wq, \
+                       wk, wv, coords, sqrt_w, K, alpha, codes, N, raw_size, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero)
 #define HEPT_FUSED_TILE(TILE)                                                                                          \
     do {                                                                                                               \
         if (Tl <= 4) HEPT_FUSED_LAUNCH(TILE, 4);                                                                       \
@@ -871,7 +872,9 @@ extern "C" int hept_prep_hash_in(const void* q, const void* k, const void* v, in
 }
 
 // internal (common.h): K as in hept_prep_hash_rpe
-int hept_prep_hash_fused_rpe(const float* x, const float* norm_w, const float* norm_b, float eps, const float* w_q,
+// ldx: row pitch of x in floats (row n starts at x + n * ldx; D for contiguous rows).  The rows are read as 16-B pieces:
+// ldx is a multiple of 4 and x 16-B aligned, HEPT_ERR_SHAPE / HEPT_ERR_ARG otherwise.
+int hept_prep_hash_fused_rpe(const float* x, int ldx, const float* norm_w, const float* norm_b, float eps, const float* w_q,
                              const float* w_k, const float* w_v, const float* coords, const float* sqrt_w, int K,
                              const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T,
                              int t0, int Tl, int precision, void* qhat, void* kvhat, float* qproj, float* kproj,
@@ -884,13 +887,15 @@ int hept_prep_hash_fused_rpe(const float* x, const float* norm_w, const float* n
         !qproj || !kproj || !minmax)
         return HEPT_ERR_ARG;
     if (H != 8 || D != 24 || N < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
+    if (ldx < D || ldx % 4 != 0) return HEPT_ERR_SHAPE;
+    if (ldx != D && (reinterpret_cast<uintptr_t>(x) & 15)) return HEPT_ERR_ARG;   // (contiguous rows: the contract is unchanged)
     if (precision == HEPT_PREC_F32_MFMA || precision == HEPT_PREC_F32_DIFF) precision = HEPT_PREC_F32;  // same f32 tile rows, another block_attn kernel
     if (precision != HEPT_PREC_F32 && precision != HEPT_PREC_BF16 && precision != HEPT_PREC_MIXED16)
         return HEPT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
 #define HEPT_FUSED_CASE(CC)                                                                                         \
     if (C == CC)                                                                                                    \
-        return launch_prep_fused<CC>(x, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, K, alpha, codes, N, raw_size, \
+        return launch_prep_fused<CC>(x, ldx, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, K, alpha, codes, N, raw_size, \
                                      T, t0, Tl, precision, qhat, kvhat, qproj, kproj, minmax, st, zero);
     HEPT_FUSED_CASE(6)
     HEPT_FUSED_CASE(4)
@@ -904,6 +909,6 @@ extern "C" int hept_prep_hash_fused(const float* x, const float* norm_w, const f
                                     const float* sqrt_w, const float* alpha, const int64_t* codes, int N, int raw_size,
                                     int H, int D, int C, int T, int t0, int Tl, int precision, void* qhat,
                                     void* kvhat, float* qproj, float* kproj, float* minmax, void* stream) {
-    return hept_prep_hash_fused_rpe(x, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, 0, alpha, codes, N, raw_size, H,
+    return hept_prep_hash_fused_rpe(x, D, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, 0, alpha, codes, N, raw_size, H,
                                     D, C, T, t0, Tl, precision, qhat, kvhat, qproj, kproj, minmax, stream, nullptr, 0);
 }

@@ -18,7 +18,8 @@ __all__ = [
     "precision_code", "rpe_scale", "prep_hash", "sort_tables", "block_attn", "reduce_tables", "combine_out",
     "forward", "forward_partial", "workspace_bytes", "profile_enable", "profile_read", "unpack_part",
     "segmented_argsort", "block_attn_bwd", "sort_tables_src", "forward_src", "forward_partial_src", "geo_args",
-    "packed_partials", "prep_hash_fused", "combine_ffn", "attn_block_forward", "attn_block_forward_src", "combine_bwd", "rpe_scale_bwd",
+    "packed_partials", "prep_hash_fused", "combine_ffn", "attn_block_forward", "attn_block_forward_src", "attn_stack_forward",
+    "attn_stack_forward_src", "combine_bwd", "rpe_scale_bwd",
     "partial_begin", "partial_heads", "combine_groups", "forward_sharded", "rows_wgrad", "ln_bwd", "ln_ffn_fwd",
     "ln_ffn_bwd",
 ]
@@ -618,14 +619,9 @@ _BLOCK_NAMES = {"norm1_w": "norm1.weight", "norm1_b": "norm1.bias", "w_q": "w_q.
                 "ff2_b": "ff.2.bias"}
 
 
-def _block_args(x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace):
-    """Checks and marshalling shared by the two one-call blocks: (x, coords, params struct, sizes, prec, workspace,
-    the tensors the struct points into)."""
-    lib = _lib.load()
-    x = _f32c(x, "x")
-    coords = _f32c(coords, "coords")
-    keep = {f: _f32c(params[k], k) for f, k in _BLOCK_NAMES.items()}
-    n, d = x.shape
+def _check_block(x_shape, coords, keep, num_heads, block_size, w_per_dist):
+    """Size checks of one block's tensors against its (N, D) input; returns (N, H, D, C, T)."""
+    n, d = x_shape
     h = num_heads
     e, t = keep["alpha"].shape[1], keep["alpha"].shape[2]
     c = e - d
@@ -640,6 +636,17 @@ def _block_args(x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2
     for f_ in ("w_q", "w_k", "w_v"):
         if tuple(keep[f_].shape) != (h * d, d):
             raise ValueError(f"{_BLOCK_NAMES[f_]} must have shape {(h * d, d)}")
+    return n, h, d, c, t
+
+
+def _block_args(x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace):
+    """Checks and marshalling shared by the two one-call blocks: (x, coords, params struct, sizes, prec, workspace,
+    the tensors the struct points into)."""
+    lib = _lib.load()
+    x = _f32c(x, "x")
+    coords = _f32c(coords, "coords")
+    keep = {f: _f32c(params[k], k) for f, k in _BLOCK_NAMES.items()}
+    n, h, d, c, t = _check_block(x.shape, coords, keep, num_heads, block_size, w_per_dist)
     prec = precision_code(precision)
     _lib.check(lib.hept_check_shape(n, h, d, c, t, block_size), "hept_check_shape")
     need = int(lib.hept_workspace_bytes(n, h, d, c, t, block_size, prec))
@@ -691,6 +698,98 @@ def attn_block_forward_src(x, coords, region_indices, regions_h, raw_size: int, 
                                                block_size, prec, workspace.data_ptr(), workspace.numel(), y.data_ptr(),
                                                _stream(x)), "hept_attn_block_forward_src")
     return y
+
+
+def _stack_args(xcat, coords, params_list, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace):
+    """Checks and marshalling shared by the two one-call stacks: the checks of ``_block_args`` for every layer, an array
+    of ``AttnParams``, and the pitch of the (N, ld) buffer (a column-sliced view is taken as it is)."""
+    lib = _lib.load()
+    if xcat.dtype != torch.float32 or xcat.dim() != 2:
+        raise TypeError(f"xcat must be a 2-d float32 tensor, got {xcat.dtype} with {xcat.dim()} dims")
+    n_layers = len(params_list)
+    if n_layers < 1:
+        raise ValueError("attn_stack_forward needs at least one layer")
+    n, cols = xcat.shape
+    # the layers write into the caller's buffer: no repairing copy here (a copy would receive the results instead)
+    if xcat.stride(1) != 1:
+        raise ValueError(f"xcat must have unit stride along its columns (stride(1) == 1), got {xcat.stride(1)}")
+    if not xcat.is_cuda:
+        raise RuntimeError(f"xcat must live on the GPU (hept_amd has no CPU path); got device {xcat.device}")
+    ld = xcat.stride(0) if n > 1 else cols
+    if cols % (n_layers + 1) != 0:
+        raise ValueError(f"xcat must have (n_layers + 1) * D = {n_layers + 1} * D columns, got {cols}")
+    d = cols // (n_layers + 1)
+    if ld < cols or ld % 4 != 0 or xcat.data_ptr() % 16:
+        raise ValueError(f"xcat needs a row pitch that is a multiple of 4 floats and a 16-byte aligned base (its rows "
+                         f"move as 16-byte pieces); got pitch {ld}, base offset {xcat.data_ptr() % 16}")
+    coords = _f32c(coords, "coords")
+    sts, keeps, dims0 = [], [], None
+    for i, params in enumerate(params_list):
+        keep = {f: _f32c(params[k], k) for f, k in _BLOCK_NAMES.items()}
+        dims = _check_block((n, d), coords, keep, num_heads, block_size, w_per_dist)
+        if dims0 is None:
+            dims0 = dims
+        elif dims != dims0:
+            raise ValueError(f"layer {i} has sizes (N, H, D, C, T) = {dims}, layer 0 has {dims0}: the layers of a stack "
+                             f"share one shape")
+        keeps.append(keep)
+        sts.append(_lib.AttnParams(**{f: v.data_ptr() for f, v in keep.items()}, eps1=float(eps1[i]), eps2=float(eps2[i])))
+    n, h, d, c, t = dims0
+    prec = precision_code(precision)
+    _lib.check(lib.hept_check_shape(n, h, d, c, t, block_size), "hept_check_shape")
+    need = int(lib.hept_workspace_bytes(n, h, d, c, t, block_size, prec))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=xcat.device, dtype=torch.uint8)
+    arr = (_lib.AttnParams * n_layers)(*sts)
+    return coords, arr, n_layers, ld, dims0, prec, workspace, keeps
+
+
+def _eps_list(eps, n_layers: int):
+    return [float(eps)] * n_layers if isinstance(eps, (int, float)) else [float(e) for e in eps]
+
+
+@_on_device
+def attn_stack_forward(xcat, coords, codes, params_list, *, num_heads: int, block_size: int, w_per_dist: int,
+                       eps1=1e-5, eps2=1e-5, precision="fp32", workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``len(params_list)`` Attn blocks in a row (the reference model's layer loop, ``example/transformer.py:119-121``,
+    eval mode) in one C call on one workspace.  ``xcat`` is (N, (L+1) D) float32 -- or a column-sliced view of a wider
+    buffer -- whose columns [0, D) hold the first layer's input; layer i writes columns [(i+1) D, (i+2) D) IN PLACE, so on
+    return ``xcat`` is the reference's ``torch.cat(all_encoded_x, dim=-1)``.  ``eps1`` / ``eps2``: one value, or one per
+    layer.  Returns ``xcat``."""
+    lib = _lib.load()
+    n_layers = len(params_list)
+    coords, arr, n_layers, ld, (n, h, d, c, t), prec, workspace, _keeps = _stack_args(
+        xcat, coords, params_list, num_heads, block_size, w_per_dist, _eps_list(eps1, n_layers),
+        _eps_list(eps2, n_layers), precision, workspace)
+    if codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n):
+        raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}")
+    codes = codes.contiguous()
+    _lib.check(lib.hept_attn_stack_forward(xcat.data_ptr(), ld, coords.data_ptr(), codes.data_ptr(), arr, n_layers, n, h,
+                                           d, c, w_per_dist, t, block_size, prec, workspace.data_ptr(),
+                                           workspace.numel(), _stream(xcat)), "hept_attn_stack_forward")
+    return xcat
+
+
+@_on_device
+def attn_stack_forward_src(xcat, coords, region_indices, regions_h, raw_size: int, params_list, *, num_heads: int,
+                           block_size: int, w_per_dist: int, eps1=1e-5, eps2=1e-5, precision="fp32",
+                           workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``attn_stack_forward`` around the src variant's operator (the layer loop of
+    ``src/models/baselines/transformer.py:133-144``); the operator's kwargs as built by ``prepare_input_src``."""
+    lib = _lib.load()
+    n_layers = len(params_list)
+    coords, arr, n_layers, ld, (n, h, d, c, t), prec, workspace, _keeps = _stack_args(
+        xcat, coords, params_list, num_heads, block_size, w_per_dist, _eps_list(eps1, n_layers),
+        _eps_list(eps2, n_layers), precision, workspace)
+    eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
+    raw_size = int(raw_size)
+    if not 0 <= raw_size <= n:
+        raise ValueError(f"raw_size must lie in [0, {n}], got {raw_size}")
+    _lib.check(lib.hept_attn_stack_forward_src(xcat.data_ptr(), ld, coords.data_ptr(), eta.data_ptr(), phi.data_ptr(),
+                                               cfac.data_ptr(), raw_size, arr, n_layers, n, h, d, c, w_per_dist, t,
+                                               block_size, prec, workspace.data_ptr(), workspace.numel(),
+                                               _stream(xcat)), "hept_attn_stack_forward_src")
+    return xcat
 
 
 @_on_device

@@ -77,7 +77,7 @@ extern "C" {
                                 take any number of tables and walk them in chunks of this size */
 #define HEPT_MAX_BLOCK 256   /* largest block_size */
 
-/* ABI version of this library (bumped on any signature change). */
+/* ABI version of this library (bumped on any signature change; a new entry point changes none and keeps it). */
 int hept_abi_version(void);
 
 /* 0 if (N,H,D,C,T_local,B) is supported by the kernels, else HEPT_ERR_SHAPE. */
@@ -392,6 +392,27 @@ int hept_attn_block_forward_src(const float* x, const float* coords, const float
                                 const float* cfac, int raw_size, const hept_attn_params* params, int N, int H,
                                 int D, int C, int K, int T, int B, int precision, void* workspace,
                                 size_t workspace_bytes, float* y, void* stream);
+
+/* The model's layer loop (example/transformer.py:119-121, src/models/baselines/transformer.py:133-144: n_layers Attn
+ * blocks in a row, every output kept, torch.cat(all_encoded_x, dim=-1) fed to W) in one call, D == 24.
+ * xcat is (N, ld) f32 with ld >= (L+1)*D: the caller has filled columns [0, D) with the encoder's output; layer i reads
+ * columns [i*D, (i+1)*D) and writes columns [(i+1)*D, (i+2)*D) of the same rows -- with ld == (L+1)*D the buffer is the
+ * reference's concatenation on return, and columns from (L+1)*D on are never touched.  coords and codes (or the geo
+ * arguments) are shared by all layers, as in the reference; layers[i] holds the parameters of layer i.
+ * ONE workspace of hept_workspace_bytes(N, H, D, C, T, B, precision) -- the size for one layer -- serves every layer:
+ * they run in order on `stream`, and a block re-initialises everything it reads there on every call.
+ * Refused before any HIP call, in this order: a null pointer (top level or inside any layer's struct) HEPT_ERR_ARG;
+ * L < 1, ld < (L+1)*D, ld % 4 != 0, D != 24, hept_check_shape, raw_size outside [0, N] HEPT_ERR_SHAPE; an xcat that
+ * is not 16-byte aligned (the rows move as 16-byte pieces; every column block is 96 bytes) or a short workspace
+ * HEPT_ERR_ARG.  A layer that fails returns its code and leaves the later columns unspecified.  hept_profile_* counts
+ * every layer as one call, like a single block. */
+int hept_attn_stack_forward(float* xcat, int ld, const float* coords, const int64_t* codes,
+                            const hept_attn_params* layers, int L, int N, int H, int D, int C, int K, int T, int B,
+                            int precision, void* workspace, size_t workspace_bytes, void* stream);
+int hept_attn_stack_forward_src(float* xcat, int ld, const float* coords, const float* eta_idx, const float* phi_idx,
+                                const float* cfac, int raw_size, const hept_attn_params* layers, int L, int N, int H,
+                                int D, int C, int K, int T, int B, int precision, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* SURVEY.md §8 f-2 — backward of the block attention (the reference trains through example/hept.py:55-80 with
  * plain autograd; there is no custom backward to mirror).  f32 tiles only; the tile products run as split-bf16
