@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "lib
 
 ABI_VERSION = 22
 PREC_F32, PREC_BF16, PREC_MIXED16, PREC_F32_MFMA, PREC_F32_DIFF = 0, 1, 2, 3, 4
-IN_F32, IN_BF16, IN_F16 = 0, 1, 2   # HEPT_IN_*: element type of q, k, v at the *_in entry points
+IN_F32, IN_BF16, IN_F16 = 0, 1, 2   # HEPT_IN_*: element type of q, k, v at the *_in entry points, of x and y at the *_io ones
 ROW = 32
 MAX_TABLES = 8
 MAX_BLOCK = 256
@@ -61,6 +61,10 @@ SIGNATURES = {
     "hept_combine_ffn": (c_int, [_P] + [c_int] * 7 + [_P] * 5 + [c_float] + [_P] * 6),
     "hept_attn_block_forward": (c_int, [_P] * 4 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
     "hept_attn_block_forward_src": (c_int, [_P] * 5 + [c_int, _P] + [c_int] * 8 + [_P, c_size_t, _P, _P]),
+    "hept_prep_hash_fused_in": (c_int, [_P, c_int] + [_P] * 2 + [c_float] + [_P] * 7 + [c_int] * 9 + [_P] * 6),
+    "hept_combine_ffn_io": (c_int, [_P] + [c_int] * 7 + [_P] * 3 + [c_int] + [_P] * 2 + [c_float] + [_P] * 6),
+    "hept_attn_block_forward_io": (c_int, [_P, c_int] + [_P] * 3 + [c_int] * 8 + [_P, c_size_t, _P, _P]),
+    "hept_attn_block_forward_src_io": (c_int, [_P, c_int] + [_P] * 4 + [c_int, _P] + [c_int] * 8 + [_P, c_size_t, _P, _P]),
     "hept_attn_stack_forward": (c_int, [_P, c_int] + [_P] * 3 + [c_int] * 9 + [_P, c_size_t, _P]),
     "hept_attn_stack_forward_src": (c_int, [_P, c_int] + [_P] * 4 + [c_int, _P] + [c_int] * 9 + [_P, c_size_t, _P]),
     "hept_combine_bwd_scratch_bytes": (c_size_t, [c_int]),

@@ -9,7 +9,10 @@ of a reference checkpoint load with ``strict=True``.
 In eval mode under ``torch.no_grad()`` the whole block is ONE C call (``hept_attn_block_forward``): LayerNorm and the
 q/k/v projections are computed while the rows of the operator are staged (q, k, v never exist in HBM: 138 MB written
 and read back per layer at tracking-60k in the unfused form), and the residual, ``norm2`` and the feed-forward run in
-the epilogue of the combine kernel.  In training mode (dropout active, gradients) the rest of the block is composed of
+the epilogue of the combine kernel.  A float32, bfloat16 or float16 ``x`` (the last two are what ``torch.autocast`` hands the
+block behind the encoder's ``nn.Linear``) goes into that call as it is and the result comes back in the same dtype: the
+kernels widen 16-bit rows where they load them and round the float32 result once where they store it, bit for bit
+``block(x.float()).to(x.dtype)`` without the two cast kernels and their float32 temporaries.  In training mode (dropout active, gradients) the rest of the block is composed of
 torch modules exactly like the reference, but ``norm1`` and the three projections are folded into the operator's row
 builder as one autograd node (``autograd.HeptPartialSumsFused``): q, k, v are never written to HBM in the forward, and
 the backward adds the small dense products behind the HIP gradients of the block attention.
@@ -103,27 +106,30 @@ class Attn(nn.Module):
             return x + self.dropout(ff_output)
         a = self.attn
         src = a.variant == "src"
+        # the one-call block reads and writes these three natively; anything else (float64) is widened / narrowed in torch
+        native = x.dtype in (torch.float32, torch.bfloat16, torch.float16)
+        xin = x if native else x.float()
         if torch.compiler.is_compiling():
             # one opaque graph node (hept_amd/library.py) instead of a ctypes call Dynamo cannot trace
             from .library import attn_block_op, attn_block_src_op
 
             if src:
                 eta, phi = kwargs["region_indices"]
-                y = attn_block_src_op(x.float(), kwargs["coords"].float(), eta, phi, kwargs["regions_h"],
+                y = attn_block_src_op(xin, kwargs["coords"].float(), eta, phi, kwargs["regions_h"],
                                       int(kwargs["raw_size"]), self.norm1.weight, self.norm1.bias, self.w_q.weight,
                                       self.w_k.weight, self.w_v.weight, self.w_rpe.weight, a.e2lsh.alpha,
                                       a.out_linear.weight, a.out_linear.bias, self.norm2.weight, self.norm2.bias,
                                       self.ff[0].weight, self.ff[0].bias, self.ff[2].weight, self.ff[2].bias,
                                       self.num_heads, a.block_size, a.num_w_per_dist, self.norm1.eps, self.norm2.eps,
                                       a.precision)
-                return y.to(x.dtype)
-            y = attn_block_op(x.float(), kwargs["coords"].float(), kwargs["combined_shifts"], self.norm1.weight,
+                return y if native else y.to(x.dtype)
+            y = attn_block_op(xin, kwargs["coords"].float(), kwargs["combined_shifts"], self.norm1.weight,
                               self.norm1.bias, self.w_q.weight, self.w_k.weight, self.w_v.weight, self.w_rpe.weight,
                               a.e2lsh.alpha, a.out_linear.weight, a.out_linear.bias, self.norm2.weight,
                               self.norm2.bias, self.ff[0].weight, self.ff[0].bias, self.ff[2].weight,
                               self.ff[2].bias, self.num_heads, a.block_size, a.num_w_per_dist, self.norm1.eps,
                               self.norm2.eps, a.precision)
-            return y.to(x.dtype)
+            return y if native else y.to(x.dtype)
         n = x.shape[0]
         c = kwargs["coords"].shape[1]
         need = ops.workspace_bytes(n, self.num_heads, self.dim_per_head, c, a.n_hashes, a.block_size, a.precision)
@@ -134,11 +140,11 @@ class Attn(nn.Module):
         common = dict(num_heads=self.num_heads, block_size=a.block_size, w_per_dist=a.num_w_per_dist,
                       eps1=self.norm1.eps, eps2=self.norm2.eps, precision=a.precision, workspace=ws)
         if src:
-            y = ops.attn_block_forward_src(x.float(), kwargs["coords"].float(), kwargs["region_indices"],
+            y = ops.attn_block_forward_src(xin, kwargs["coords"].float(), kwargs["region_indices"],
                                            kwargs["regions_h"], kwargs["raw_size"], params, **common)
         else:
-            y = ops.attn_block_forward(x.float(), kwargs["coords"].float(), kwargs["combined_shifts"], params, **common)
-        return y.to(x.dtype)
+            y = ops.attn_block_forward(xin, kwargs["coords"].float(), kwargs["combined_shifts"], params, **common)
+        return y if native else y.to(x.dtype)
 
 
 class SrcAttn(Attn):

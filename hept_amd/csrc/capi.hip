@@ -683,13 +683,19 @@ int attn_params_check(const hept_attn_params* p) {
 // the whole Attn block for either variant: geo.eta == nullptr takes the example variant's AND codes, else the src
 // variant's region shift and padding rows (rows >= geo.raw_size: zero q^, k^, v, hash +inf; the residual and the
 // feed-forward still run on them, as in the reference's block).
-// ldx / ldy: row pitches of x and y in floats (D, D: the contiguous (N, D) tensors of hept_attn_block_forward).
-int attn_block_impl(const float* x, int ldx, const float* coords, const int64_t* codes, const GeoShift& geo,
+// x and y hold elements of io_dtype (HEPT_IN_*): 16-bit rows are widened where they are loaded and the f32 result is
+// rounded once where it is stored; everything in between is the f32 block.
+// ldx / ldy: row pitches of x and y in such elements (D, D: the contiguous (N, D) tensors of hept_attn_block_forward).
+int attn_block_impl(const void* x, int io_dtype, int ldx, const float* coords, const int64_t* codes, const GeoShift& geo,
                     const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B, int precision,
-                    void* workspace, size_t workspace_bytes, float* y, int ldy, void* stream) {
+                    void* workspace, size_t workspace_bytes, void* y, int ldy, void* stream) {
     if (!x || !coords || !p || !workspace || !y) return HEPT_ERR_ARG;
     int rc = attn_params_check(p);
     if (rc) return rc;
+    if (io_dtype != HEPT_IN_F32 && io_dtype != HEPT_IN_BF16 && io_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
+    // 16-bit rows move as 16-B (x) and 8-B (y) pieces: refused here, before the row builder has run for nothing
+    if (io_dtype != HEPT_IN_F32 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
+        return HEPT_ERR_ARG;
     rc = hept_check_shape(N, H, D, C, T, B);
     if (rc) return rc;
     if (D != 24) return HEPT_ERR_SHAPE;
@@ -708,7 +714,7 @@ int attn_block_impl(const float* x, int ldx, const float* coords, const int64_t*
         void* zptr = nullptr;
         size_t zbytes = 0;
         hept_sort_zero_block(w.sort_ws, N, H, tc, &zptr, &zbytes);   // (see run_begin)
-        rc = hept_prep_hash_fused_rpe(x, ldx, p->norm1_w, p->norm1_b, p->eps1, p->w_q, p->w_k, p->w_v, coords, p->w_rpe, K,
+        rc = hept_prep_hash_fused_rpe(x, io_dtype, ldx, p->norm1_w, p->norm1_b, p->eps1, p->w_q, p->w_k, p->w_v, coords, p->w_rpe, K,
                                       p->alpha, codes, N, raw_size, H, D, C, T, c0, tc, precision, w.qhat, w.kvhat, w.qproj,
                                       w.kproj, w.minmax, stream, zptr, zbytes);
         if (rc) return rc;
@@ -732,8 +738,8 @@ int attn_block_impl(const float* x, int ldx, const float* coords, const int64_t*
     rc = hept_block_attn(w.qhat, w.kvhat, qpos, kpos, N, H, D, T, B, precision, w.part, stream);
     if (rc) return rc;
     prof_mark(3, st);
-    rc = hept_combine_ffn_ld(w.part, hept_part_precision(precision, D), T, N, H, D, 0, N, p->out_w, p->out_b, x, ldx,
-                             p->norm2_w, p->norm2_b, p->eps2, p->ff1_w, p->ff1_b, p->ff2_w, p->ff2_b, y, ldy, stream);
+    rc = hept_combine_ffn_ld(w.part, hept_part_precision(precision, D), T, N, H, D, 0, N, p->out_w, p->out_b, x, io_dtype,
+                             ldx, p->norm2_w, p->norm2_b, p->eps2, p->ff1_w, p->ff1_b, p->ff2_w, p->ff2_b, y, ldy, stream);
     prof_mark(4, st);
     prof_call_done();
     return rc;
@@ -760,7 +766,7 @@ int attn_stack_impl(float* xcat, int ld, const float* coords, const int64_t* cod
     if (workspace_bytes < carve(nullptr, N, H, C, T, precision).bytes) return HEPT_ERR_ARG;
     for (int i = 0; i < L; ++i) {
         // (each layer is one profiled call, like a single block: stage times per block stay comparable)
-        rc = attn_block_impl(xcat + (size_t)i * D, ld, coords, codes, geo, layers + i, N, H, D, C, K, T, B, precision,
+        rc = attn_block_impl(xcat + (size_t)i * D, HEPT_IN_F32, ld, coords, codes, geo, layers + i, N, H, D, C, K, T, B, precision,
                              workspace, workspace_bytes, xcat + (size_t)(i + 1) * D, ld, stream);
         if (rc) return rc;
     }
@@ -768,13 +774,32 @@ int attn_stack_impl(float* xcat, int ld, const float* coords, const int64_t* cod
 }
 }  // namespace
 
+extern "C" int hept_attn_block_forward_io(const void* x, int io_dtype, const float* coords, const int64_t* codes,
+                                          const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B,
+                                          int precision, void* workspace, size_t workspace_bytes, void* y,
+                                          void* stream) {
+    if (!codes) return HEPT_ERR_ARG;
+    return attn_block_impl(x, io_dtype, D, coords, codes, GeoShift{}, p, N, H, D, C, K, T, B, precision, workspace,
+                           workspace_bytes, y, D, stream);
+}
+
 extern "C" int hept_attn_block_forward(const float* x, const float* coords, const int64_t* codes,
                                        const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B,
                                        int precision, void* workspace, size_t workspace_bytes, float* y,
                                        void* stream) {
-    if (!codes) return HEPT_ERR_ARG;
-    return attn_block_impl(x, D, coords, codes, GeoShift{}, p, N, H, D, C, K, T, B, precision, workspace, workspace_bytes,
-                           y, D, stream);
+    return hept_attn_block_forward_io(x, HEPT_IN_F32, coords, codes, p, N, H, D, C, K, T, B, precision, workspace,
+                                      workspace_bytes, y, stream);
+}
+
+extern "C" int hept_attn_block_forward_src_io(const void* x, int io_dtype, const float* coords, const float* eta_idx,
+                                              const float* phi_idx, const float* cfac, int raw_size,
+                                              const hept_attn_params* p, int N, int H, int D, int C, int K, int T,
+                                              int B, int precision, void* workspace, size_t workspace_bytes, void* y,
+                                              void* stream) {
+    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
+    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
+    return attn_block_impl(x, io_dtype, D, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, p, N, H, D, C, K,
+                           T, B, precision, workspace, workspace_bytes, y, D, stream);
 }
 
 extern "C" int hept_attn_block_forward_src(const float* x, const float* coords, const float* eta_idx,
@@ -782,10 +807,8 @@ extern "C" int hept_attn_block_forward_src(const float* x, const float* coords, 
                                            const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B,
                                            int precision, void* workspace, size_t workspace_bytes, float* y,
                                            void* stream) {
-    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
-    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return attn_block_impl(x, D, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, p, N, H, D, C, K, T, B,
-                           precision, workspace, workspace_bytes, y, D, stream);
+    return hept_attn_block_forward_src_io(x, HEPT_IN_F32, coords, eta_idx, phi_idx, cfac, raw_size, p, N, H, D, C, K, T, B,
+                                          precision, workspace, workspace_bytes, y, stream);
 }
 
 extern "C" int hept_attn_stack_forward(float* xcat, int ld, const float* coords, const int64_t* codes,

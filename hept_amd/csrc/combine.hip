@@ -77,7 +77,7 @@ struct RawRow {
 // aggregated rows goes through a wave-private LDS tile so that lane (point, half) holds a whole row; each half
 // computes 12 hidden and 12 output units (weights are LDS broadcasts), the halves swap hidden units by shuffle.
 struct FfnIn {
-    const float* x;      // (n_count, D) block input rows, row n0 first, at row pitch ldx floats
+    const void* x;       // (n_count, D) block input rows of the kernel's IO type, row n0 first, at row pitch ldx elements
     const float* ln_w;   // norm2.weight, norm2.bias
     const float* ln_b;
     const float* w1;     // ff.0.weight (D, D), ff.0.bias
@@ -85,9 +85,10 @@ struct FfnIn {
     const float* w2;     // ff.2.weight (D, D), ff.2.bias
     const float* b2;
     float eps;
-    // Row pitches (floats) of x and of the output y; FFN_D for contiguous rows.  An AttnStack layer reads and writes
+    // Row pitches (elements of the IO type) of x and of the output y; FFN_D for contiguous rows.  An AttnStack layer reads and writes
     // different column blocks of the SAME rows of one (N, ld) buffer (ldx == ldy == ld): x and y then interleave in
-    // memory but never share a byte, so the __restrict__ on `out` stays valid.  Multiples of 4 (16-B pieces).
+    // memory but never share a byte, so the __restrict__ on `out` stays valid.  Multiples of 4 (16-B pieces of f32 rows),
+    // of 8 for 16-bit rows.
     int ldx, ldy;
 };
 constexpr int FFN_D = 24, FFN_PITCH = 25, FFN_WFLOATS = 2 * FFN_D * FFN_D + 4 * FFN_D;
@@ -113,6 +114,10 @@ constexpr int FFN_D = 24, FFN_PITCH = 25, FFN_WFLOATS = 2 * FFN_D * FFN_D + 4 * 
 // ds_read_b128 (pieces XOR-permuted by the point on the SOURCE side, so that 16 lanes hit 16 bank groups).  The next
 // head pair's loads are issued as soon as the current rows are in registers: the prefetch lives in LDS (12 KB per
 // wave), not in a second register set.
+// IO (HEPT_IN_*, FFN only): element type of the block input ffn.x AND of the output rows.  A 16-bit row is 48 B: the
+// epilogue reads it as three 16-B pieces widened to the same f32 values `.float()` gives, and the f32 result is rounded
+// once (to nearest even; fp16 overflow to inf) on its way out -- a lane half owns bytes [24 hh, 24 hh + 24) of the row,
+// 8-B but not 16-B aligned: three 8-B stores.  Everything in between is the f32 code.
 constexpr int STG_TABLE_BYTES = 32 * 8 * 16;             // packed rows: one table, one head pair, 32 points
 constexpr int STG_WAVE_BYTES = 3 * STG_TABLE_BYTES;      // up to three tables in flight
 // f32 rows (128 B): the image of ONE (table, head pair) unit is 32 points x 256 B = 8 KB, so the tables of a head pair
@@ -121,7 +126,8 @@ constexpr int STG_WAVE_BYTES = 3 * STG_TABLE_BYTES;      // up to three tables i
 // weight column comes straight from W (no slab: 64 KB of images per workgroup, two workgroups per CU).
 constexpr int STG32_UNIT_BYTES = 32 * 16 * 16;
 constexpr int STG32_WAVE_BYTES = 2 * STG32_UNIT_BYTES;
-template <bool P16, bool FFN = false, int DT = 0, bool SPLIT = false, bool PUSH = false, bool STG = false>
+template <bool P16, bool FFN = false, int DT = 0, bool SPLIT = false, bool PUSH = false, bool STG = false,
+          int IO = HEPT_IN_F32>
 __global__ __launch_bounds__(CMB_THREADS) void combine_out_kernel(const float* __restrict__ part, int Tl, int N,
                                                                   int H, int D_rt, int n0, int n_count,
                                                                   const float* __restrict__ W,
@@ -131,6 +137,7 @@ __global__ __launch_bounds__(CMB_THREADS) void combine_out_kernel(const float* _
                                                                   int stg_off = 0) {
     static_assert(!PUSH || (DT == 24 && !FFN), "the pushing epilogue is built for D = 24 rows");
     static_assert(!STG || DT == 24, "staged rows: D = 24");
+    static_assert(FFN || IO == HEPT_IN_F32, "only the block epilogue reads and writes 16-bit rows");
     constexpr int ROWF = P16 ? 16 : 32;   // row pitch in 4-byte units
     extern __shared__ __attribute__((aligned(16))) float wt_s[];  // [H (even-padded)][28 (d)][32 (c, zero padded)]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, li = lane & 31;
@@ -399,13 +406,28 @@ __global__ __launch_bounds__(CMB_THREADS) void combine_out_kernel(const float* _
                 if (li < FFN_D) stage_s[hept_acc_row(r, hh) * FFN_PITCH + li] = acc[r] + bia;
             // (one wave's LDS accesses execute in order: the tile is complete when the reads below are issued)
             const bool valid = i < n_count;
-            const f32x4* xs = reinterpret_cast<const f32x4*>(ffn.x + (size_t)(valid ? i : n_count - 1) * ffn.ldx);
+            const size_t xrow = (size_t)(valid ? i : n_count - 1) * ffn.ldx;
             float y1[FFN_D];
+            if constexpr (IO != HEPT_IN_F32) {
+                const u32x4* xs = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(ffn.x) + xrow);
 #pragma unroll
-            for (int j = 0; j < FFN_D / 4; ++j) {
-                const f32x4 xv = xs[j];
+                for (int j = 0; j < FFN_D / 8; ++j) {
+                    const u32x4 x8 = xs[j];
+                    const f32x4 lo = hept_widen4<IO>(x8[0], x8[1]), hi = hept_widen4<IO>(x8[2], x8[3]);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) y1[4 * j + u] = xv[u] + stage_s[li * FFN_PITCH + 4 * j + u];
+                    for (int u = 0; u < 4; ++u) {
+                        y1[8 * j + u] = lo[u] + stage_s[li * FFN_PITCH + 8 * j + u];
+                        y1[8 * j + 4 + u] = hi[u] + stage_s[li * FFN_PITCH + 8 * j + 4 + u];
+                    }
+                }
+            } else {
+                const f32x4* xs = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(ffn.x) + xrow);
+#pragma unroll
+                for (int j = 0; j < FFN_D / 4; ++j) {
+                    const f32x4 xv = xs[j];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) y1[4 * j + u] = xv[u] + stage_s[li * FFN_PITCH + 4 * j + u];
+                }
             }
             float mean = 0.f;
 #pragma unroll
@@ -448,17 +470,34 @@ __global__ __launch_bounds__(CMB_THREADS) void combine_out_kernel(const float* _
                 yo[uu] = a;
             }
             if (valid) {
-                f32x4* dst = reinterpret_cast<f32x4*>(out + (size_t)i * ffn.ldy + hh * (FFN_D / 2));
+                if constexpr (IO != HEPT_IN_F32) {
+                    u32x2* dst = reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(out) + (size_t)i * ffn.ldy +
+                                                          hh * (FFN_D / 2));
+                    f32x4 o[FFN_D / 8];   // (all twelve sums first, then the three stores: fewer live registers than store by store)
 #pragma unroll
-                for (int c4 = 0; c4 < FFN_D / 8; ++c4) {
-                    f32x4 o;
+                    for (int c4 = 0; c4 < FFN_D / 8; ++c4) {
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        // y1[12 hh + 4 c4 + u] with a compile-time index in both halves
-                        const float res = hh ? y1[FFN_D / 2 + 4 * c4 + u] : y1[4 * c4 + u];
-                        o[u] = res + yo[4 * c4 + u];
+                        for (int u = 0; u < 4; ++u) {
+                            const float res = hh ? y1[FFN_D / 2 + 4 * c4 + u] : y1[4 * c4 + u];
+                            o[c4][u] = res + yo[4 * c4 + u];
+                        }
                     }
-                    dst[c4] = o;
+#pragma unroll
+                    for (int c4 = 0; c4 < FFN_D / 8; ++c4)
+                        dst[c4] = u32x2{hept_narrow2<IO>(o[c4][0], o[c4][1]), hept_narrow2<IO>(o[c4][2], o[c4][3])};
+                } else {
+                    f32x4* dst = reinterpret_cast<f32x4*>(out + (size_t)i * ffn.ldy + hh * (FFN_D / 2));
+#pragma unroll
+                    for (int c4 = 0; c4 < FFN_D / 8; ++c4) {
+                        f32x4 o;
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            // y1[12 hh + 4 c4 + u] with a compile-time index in both halves
+                            const float res = hh ? y1[FFN_D / 2 + 4 * c4 + u] : y1[4 * c4 + u];
+                            o[u] = res + yo[4 * c4 + u];
+                        }
+                        dst[c4] = o;
+                    }
                 }
             }
         } else if constexpr (PUSH) {
@@ -901,7 +940,7 @@ inline bool staged_combine_off() {
 }
 
 constexpr int CMB_NO_LDS = -1;   // internal: the device refused the staged rows' LDS size (never leaves this file)
-template <bool P16, bool FFN, int DT, bool PUSH, bool STG>
+template <bool P16, bool FFN, int DT, bool PUSH, bool STG, int IO>
 int combine_launch_impl(hipStream_t st, const float* part, int Tl, int N, int H, int D, int n0, int n_count,
                         const float* W, const float* b, float* out, const FfnIn& ffn, int HG, size_t gstride,
                         const P2pDev& px) {
@@ -918,25 +957,25 @@ int combine_launch_impl(hipStream_t st, const float* part, int Tl, int N, int H,
     if (lds > 65536) {   // many heads (the weight slab alone is 3.6 KiB per head), or the staged rows' images
         static LdsRaised raised_split, raised_flat;
         if (hept_raise_lds(split ? raised_split : raised_flat,
-                           split ? reinterpret_cast<const void*>(&combine_out_kernel<P16, FFN, DT, true, PUSH, STG>)
-                                 : reinterpret_cast<const void*>(&combine_out_kernel<P16, FFN, DT, false, PUSH, STG>), lds))
+                           split ? reinterpret_cast<const void*>(&combine_out_kernel<P16, FFN, DT, true, PUSH, STG, IO>)
+                                 : reinterpret_cast<const void*>(&combine_out_kernel<P16, FFN, DT, false, PUSH, STG, IO>), lds))
             return STG ? CMB_NO_LDS : HEPT_ERR_LAUNCH;   // (staged rows: the caller takes the lane-by-lane kernel instead)
     }
     if (split) {
-        hipLaunchKernelGGL((combine_out_kernel<P16, FFN, DT, true, PUSH, STG>), dim3(n_tiles < HEPT_CMB_SPLIT_GRID ? n_tiles : HEPT_CMB_SPLIT_GRID), dim3(CMB_THREADS), lds, st, part,
+        hipLaunchKernelGGL((combine_out_kernel<P16, FFN, DT, true, PUSH, STG, IO>), dim3(n_tiles < HEPT_CMB_SPLIT_GRID ? n_tiles : HEPT_CMB_SPLIT_GRID), dim3(CMB_THREADS), lds, st, part,
                            Tl, N, H, D, n0, n_count, W, b, out, HG, gstride, ffn, px, stg_off);
     } else {
         const int wgs = (n_tiles + CMB_WAVES - 1) / CMB_WAVES;
 #ifndef HEPT_CMB_MAX_WGS
 #define HEPT_CMB_MAX_WGS 2048
 #endif
-        hipLaunchKernelGGL((combine_out_kernel<P16, FFN, DT, false, PUSH, STG>), dim3(wgs < HEPT_CMB_MAX_WGS ? wgs : HEPT_CMB_MAX_WGS), dim3(CMB_THREADS),
+        hipLaunchKernelGGL((combine_out_kernel<P16, FFN, DT, false, PUSH, STG, IO>), dim3(wgs < HEPT_CMB_MAX_WGS ? wgs : HEPT_CMB_MAX_WGS), dim3(CMB_THREADS),
                            lds, st, part, Tl, N, H, D, n0, n_count, W, b, out, HG, gstride, ffn, px, stg_off);
     }
     return hept_launch_status();
 }
 
-template <bool P16, bool FFN, int DT, bool PUSH = false>
+template <bool P16, bool FFN, int DT, bool PUSH = false, int IO = HEPT_IN_F32>
 int combine_launch(hipStream_t st, const float* part, int Tl, int N, int H, int D, int n0, int n_count, const float* W,
                    const float* b, float* out, const FfnIn& ffn, int HG = 0, size_t gstride = 0,
                    const P2pDev& px = P2pDev{}) {
@@ -948,11 +987,11 @@ int combine_launch(hipStream_t st, const float* part, int Tl, int N, int H, int 
     // a point's slot) -- the plain layout, and the receive region of the table-sharded step (PUSH; "tables" = source ranks)
     if constexpr (DT == 24) {
         if (HG % 2 == 0 && H % 2 == 0 && !staged_combine_off()) {
-            const int rc = combine_launch_impl<P16, FFN, DT, PUSH, true>(st, part, Tl, N, H, D, n0, n_count, W, b, out, ffn, HG, gstride, px);
+            const int rc = combine_launch_impl<P16, FFN, DT, PUSH, true, IO>(st, part, Tl, N, H, D, n0, n_count, W, b, out, ffn, HG, gstride, px);
             if (rc != CMB_NO_LDS) return rc;   // (the raise of the dynamic LDS limit failed: lane-by-lane loads need less)
         }
     }
-    return combine_launch_impl<P16, FFN, DT, PUSH, false>(st, part, Tl, N, H, D, n0, n_count, W, b, out, ffn, HG, gstride, px);
+    return combine_launch_impl<P16, FFN, DT, PUSH, false, IO>(st, part, Tl, N, H, D, n0, n_count, W, b, out, ffn, HG, gstride, px);
 }
 
 extern "C" int hept_combine_groups(const float* part, int part_precision, int Tl, int N, int H, int D, int n0,
@@ -998,36 +1037,54 @@ extern "C" int hept_combine_out(const float* part, int part_precision, int Tl, i
     return hept_combine_groups(part, part_precision, Tl, N, H, D, n0, n_count, H, 0, out_weight, out_bias, out, stream);
 }
 
-// internal (common.h): hept_combine_ffn with row pitches ldx / ldy (floats) for x and y -- row n of x starts at
-// x + n * ldx.  Multiples of 4 with 16-B aligned bases (the rows move as 16-B pieces); FFN_D, FFN_D is hept_combine_ffn.
+// internal (common.h): hept_combine_ffn_io with row pitches ldx / ldy for x and y, in elements of io_dtype -- row n of x
+// starts at element n * ldx.  f32: multiples of 4 with 16-B aligned bases (the rows move as 16-B pieces); FFN_D, FFN_D is
+// hept_combine_ffn.  16-bit rows: multiples of 8 and 16-B aligned bases at any pitch (x moves as 16-B pieces, y as 8-B ones).
 int hept_combine_ffn_ld(const float* part, int part_precision, int Tl, int N, int H, int D, int n0, int n_count,
-                        const float* out_weight, const float* out_bias, const float* x, int ldx, const float* norm_w,
-                        const float* norm_b, float eps, const float* ff1_w, const float* ff1_b, const float* ff2_w,
-                        const float* ff2_b, float* y, int ldy, void* stream) {
+                        const float* out_weight, const float* out_bias, const void* x, int io_dtype, int ldx,
+                        const float* norm_w, const float* norm_b, float eps, const float* ff1_w, const float* ff1_b,
+                        const float* ff2_w, const float* ff2_b, void* y, int ldy, void* stream) {
     if (!part || !out_weight || !x || !norm_w || !norm_b || !ff1_w || !ff1_b || !ff2_w || !ff2_b || !y)
         return HEPT_ERR_ARG;
+    if (io_dtype != HEPT_IN_F32 && io_dtype != HEPT_IN_BF16 && io_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
+    const bool io16 = io_dtype != HEPT_IN_F32;
     if (Tl < 1 || N < 1 || H < 1 || H > 16 || D != FFN_D || n0 < 0 || n_count < 0 || n0 + n_count > N)
         return HEPT_ERR_SHAPE;
-    if (ldx < FFN_D || ldy < FFN_D || ldx % 4 != 0 || ldy % 4 != 0) return HEPT_ERR_SHAPE;
-    // (contiguous rows keep the contract they had; pitched rows come from the stack entry, which has checked its buffer)
-    if ((ldx != FFN_D || ldy != FFN_D) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
+    const int piece = io16 ? 8 : 4;
+    if (ldx < FFN_D || ldy < FFN_D || ldx % piece != 0 || ldy % piece != 0) return HEPT_ERR_SHAPE;
+    // (contiguous f32 rows keep the contract they had; pitched rows come from the stack entry, which has checked its buffer)
+    if ((io16 || ldx != FFN_D || ldy != FFN_D) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
         return HEPT_ERR_ARG;
     if (n_count == 0) return HEPT_OK;
     hipStream_t st = (hipStream_t)stream;
     const FfnIn ffn{x, norm_w, norm_b, ff1_w, ff1_b, ff2_w, ff2_b, eps, ldx, ldy};
-    if (part_precision == HEPT_PREC_BF16)
-        return combine_launch<true, true, 24>(st, part, Tl, N, H, D, n0, n_count, out_weight, out_bias, y, ffn);
-    if (part_precision == HEPT_PREC_F32)
-        return combine_launch<false, true, 24>(st, part, Tl, N, H, D, n0, n_count, out_weight, out_bias, y, ffn);
-    return HEPT_ERR_SHAPE;
+    float* out = reinterpret_cast<float*>(y);   // (the kernel's IO type says what the rows hold)
+    const bool p16 = part_precision == HEPT_PREC_BF16;
+    if (!p16 && part_precision != HEPT_PREC_F32) return HEPT_ERR_SHAPE;
+#define HEPT_FFN_IO(IO)                                                                                                 \
+    return p16 ? combine_launch<true, true, 24, false, IO>(st, part, Tl, N, H, D, n0, n_count, out_weight, out_bias, out, ffn) \
+               : combine_launch<false, true, 24, false, IO>(st, part, Tl, N, H, D, n0, n_count, out_weight, out_bias, out, ffn)
+    if (io_dtype == HEPT_IN_BF16) HEPT_FFN_IO(HEPT_IN_BF16);
+    if (io_dtype == HEPT_IN_F16) HEPT_FFN_IO(HEPT_IN_F16);
+    HEPT_FFN_IO(HEPT_IN_F32);
+#undef HEPT_FFN_IO
+}
+
+extern "C" int hept_combine_ffn_io(const float* part, int part_precision, int Tl, int N, int H, int D, int n0,
+                                   int n_count, const float* out_weight, const float* out_bias, const void* x,
+                                   int io_dtype, const float* norm_w, const float* norm_b, float eps,
+                                   const float* ff1_w, const float* ff1_b, const float* ff2_w, const float* ff2_b,
+                                   void* y, void* stream) {
+    return hept_combine_ffn_ld(part, part_precision, Tl, N, H, D, n0, n_count, out_weight, out_bias, x, io_dtype, FFN_D,
+                               norm_w, norm_b, eps, ff1_w, ff1_b, ff2_w, ff2_b, y, FFN_D, stream);
 }
 
 extern "C" int hept_combine_ffn(const float* part, int part_precision, int Tl, int N, int H, int D, int n0,
                                 int n_count, const float* out_weight, const float* out_bias, const float* x,
                                 const float* norm_w, const float* norm_b, float eps, const float* ff1_w,
                                 const float* ff1_b, const float* ff2_w, const float* ff2_b, float* y, void* stream) {
-    return hept_combine_ffn_ld(part, part_precision, Tl, N, H, D, n0, n_count, out_weight, out_bias, x, FFN_D, norm_w,
-                               norm_b, eps, ff1_w, ff1_b, ff2_w, ff2_b, y, FFN_D, stream);
+    return hept_combine_ffn_io(part, part_precision, Tl, N, H, D, n0, n_count, out_weight, out_bias, x, HEPT_IN_F32,
+                               norm_w, norm_b, eps, ff1_w, ff1_b, ff2_w, ff2_b, y, stream);
 }
 
 static bool combine_bwd_tuned(int H, int D) { return D == CB_D && H <= 8; }   // the shipped models' rows

@@ -90,6 +90,12 @@ __device__ __forceinline__ unsigned int hept_pack_f16(float lo, float hi) {
     const hept_f32x2 v = {fminf(fmaxf(lo, -65504.f), 65504.f), fminf(fmaxf(hi, -65504.f), 65504.f)};
     return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, hept_f16x2));
 }
+// ... and the IEEE form: a value beyond the largest finite fp16 becomes +-inf, results below 2^-14 become subnormals (the
+// kernels run with fp16 denormals on, see below) -- what torch's `.to(torch.float16)` gives
+__device__ __forceinline__ unsigned int hept_pack_f16_ieee(float lo, float hi) {
+    const hept_f32x2 v = {lo, hi};
+    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, hept_f16x2));
+}
 __device__ __forceinline__ float hept_f16_lo(unsigned int w) { return (float)__builtin_bit_cast(hept_f16x2, w)[0]; }
 __device__ __forceinline__ float hept_f16_hi(unsigned int w) { return (float)__builtin_bit_cast(hept_f16x2, w)[1]; }
 
@@ -112,6 +118,13 @@ __device__ __forceinline__ float hept_in_hi(unsigned int w) {
 template <int IN>
 __device__ __forceinline__ f32x4 hept_widen4(unsigned int w0, unsigned int w1) {   // 4 consecutive elements
     return f32x4{hept_in_lo<IN>(w0), hept_in_hi<IN>(w0), hept_in_lo<IN>(w1), hept_in_hi<IN>(w1)};
+}
+// the way back, for a block output of the input's type (combine.hip, FFN epilogue): one rounding to nearest even, fp16
+// overflow to +-inf
+template <int IN>
+__device__ __forceinline__ unsigned int hept_narrow2(float lo, float hi) {
+    if constexpr (IN == HEPT_IN_BF16) return hept_pack_bf16(lo, hi);
+    else return hept_pack_f16_ieee(lo, hi);
 }
 // one element of a 16-bit array (2-byte aligned), or of an f32 array
 template <int IN>
@@ -244,16 +257,17 @@ int hept_prep_hash_rpe(const void* q, const void* k, const void* v, const float*
                        void* stream, int roles = 3,   // roles == 2: q and k rows + hashes only (the v rows: HeptRowsJob)
                        void* zero_ptr = nullptr, size_t zero_bytes = 0,   // scratch the launch clears on its way (hept_sort_zero_block)
                        int in_dtype = HEPT_IN_F32);
-int hept_prep_hash_fused_rpe(const float* x, int ldx, const float* norm_w, const float* norm_b, float eps, const float* w_q,
+// x: rows of element type io_dtype (HEPT_IN_*) at a pitch of ldx elements
+int hept_prep_hash_fused_rpe(const void* x, int io_dtype, int ldx, const float* norm_w, const float* norm_b, float eps, const float* w_q,
                              const float* w_k, const float* w_v, const float* coords, const float* sqrt_w, int K,
                              const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T,
                              int t0, int Tl, int precision, void* qhat, void* kvhat, float* qproj, float* kproj,
                              float* minmax, void* stream, void* zero_ptr = nullptr, size_t zero_bytes = 0);
-// hept_combine_ffn with row pitches (floats) for x and y (combine.hip)
+// hept_combine_ffn_io with row pitches for x and y, in elements of io_dtype (combine.hip)
 int hept_combine_ffn_ld(const float* part, int part_precision, int Tl, int N, int H, int D, int n0, int n_count,
-                        const float* out_weight, const float* out_bias, const float* x, int ldx, const float* norm_w,
-                        const float* norm_b, float eps, const float* ff1_w, const float* ff1_b, const float* ff2_w,
-                        const float* ff2_b, float* y, int ldy, void* stream);
+                        const float* out_weight, const float* out_bias, const void* x, int io_dtype, int ldx,
+                        const float* norm_w, const float* norm_b, float eps, const float* ff1_w, const float* ff1_b,
+                        const float* ff2_w, const float* ff2_b, void* y, int ldy, void* stream);
 // The v half of the kvhat rows written by workgroups that ride in the bucket-sort launch (sort_tables.hip) instead of by
 // the row builder's third role: hept_prep_hash_rpe with roles == 2 leaves them out, hept_sort_tables_rows /
 // hept_sort_tables_src_rows with a job description write them.  hept_sort_carries_rows: the sort of N-key segments has

@@ -160,13 +160,15 @@ struct FusedIn {
     const float* ln_b;   // norm1.bias (D)
     const float* w_s;    // LDS: this role's projection weight, [h][j][d] (transposed) at head pitch FUSED_WPITCH
     float eps;
-    int ldx;             // row pitch of x in floats (D: contiguous rows; a multiple of 4: the rows are read as 16-B pieces)
+    int ldx;             // row pitch of x in ELEMENTS of its type (D: contiguous rows); the rows are read as 16-B pieces:
+                         // a multiple of 4 for f32 rows, of 8 for 16-bit rows
 };
 constexpr int FUSED_WPITCH = 24 * 24 + 4;  // head pitch = 4 (mod 32) dwords: the 8 heads' 16-B reads hit 8 distinct bank groups
 
 // IN (HEPT_IN_*): element type of x.  16-bit inputs: the wave's run is 3 KiB at H*D = 192, fetched as 16-B pieces of 8
 // elements (3 / 2 / 1 loads per lane at D = 24 / 16 / 8), each widened in registers to the two f32 chunks it holds and
-// written to their two LDS slots -- everything after the LDS read-back is the f32 code.
+// written to their two LDS slots -- everything after the LDS read-back is the f32 code.  FUSED: a lane reads its point's
+// whole row itself, D = 24 elements = six 16-B pieces of f32 or three of a 16-bit type, widened into the same xv[24].
 template <int D, int C, int TILE, int ROLE, int TMAX, bool FUSED = false, int IN = HEPT_IN_F32>
 __device__ __forceinline__ void prep_role(const void* __restrict__ x_, const float* __restrict__ coords,
                                           const float* __restrict__ sw_s, const float* __restrict__ alpha_s,
@@ -184,7 +186,6 @@ __device__ __forceinline__ void prep_role(const void* __restrict__ x_, const flo
     constexpr int ROWOFF = ROLE == 2 ? QROW : 0;        // v lives in the second half of a kvhat row
     constexpr int CH = QROW / 16;                       // 16-B chunks per finished row
     constexpr bool IN16 = IN != HEPT_IN_F32;
-    static_assert(!(FUSED && IN16), "the fused row builder reads f32 activations");
     // input pieces of 16 B per lane: 4 floats (6 at D = 24), or 8 16-bit elements = f32 chunks 2c and 2c + 1 (3)
     constexpr int LOADS = PREP_POINTS * HD / (IN16 ? 8 : 4) / HEPT_WAVE;
     static_assert(D4 % 2 == 0 || !IN16, "an 8-element piece must not straddle a head row");
@@ -229,11 +230,22 @@ __device__ __forceinline__ void prep_role(const void* __restrict__ x_, const flo
         f32x4 xr[D4];
         if constexpr (FUSED) {
             float xv[D];
-            const f32x4* xs = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x_) + (size_t)(live ? n : n0) * fin.ldx);
+            if constexpr (IN16) {
+                const u32x4* xs = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(x_) + (size_t)(live ? n : n0) * fin.ldx);
 #pragma unroll
-            for (int j = 0; j < D4; ++j) {
-                const f32x4 v4 = xs[j];
-                xv[4 * j] = v4[0]; xv[4 * j + 1] = v4[1]; xv[4 * j + 2] = v4[2]; xv[4 * j + 3] = v4[3];
+                for (int j = 0; j < D / 8; ++j) {
+                    const u32x4 v8 = xs[j];
+                    const f32x4 lo = hept_widen4<IN>(v8[0], v8[1]), hi = hept_widen4<IN>(v8[2], v8[3]);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) { xv[8 * j + u] = lo[u]; xv[8 * j + 4 + u] = hi[u]; }
+                }
+            } else {
+                const f32x4* xs = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x_) + (size_t)(live ? n : n0) * fin.ldx);
+#pragma unroll
+                for (int j = 0; j < D4; ++j) {
+                    const f32x4 v4 = xs[j];
+                    xv[4 * j] = v4[0]; xv[4 * j + 1] = v4[1]; xv[4 * j + 2] = v4[2]; xv[4 * j + 3] = v4[3];
+                }
             }
             float mean = 0.f;
 #pragma unroll
@@ -531,11 +543,12 @@ void prep_hash_kernel(
 
 // Attn-block front end: LayerNorm + the three projections fused into the row builder (D = 24 only)
 // 16-bit rows, 4 table slots: 39.9 KB of LDS = 4 workgroups per CU, and the registers are held to that occupancy too
-template <int C, int TILE, int TMAX>
+// IN (HEPT_IN_*): element type of x, as in prep_role
+template <int C, int TILE, int TMAX, int IN>
 __global__ __launch_bounds__(PREP_THREADS)
 __attribute__((amdgpu_waves_per_eu((TILE != HEPT_PREC_F32 && TMAX == 4) ? (C == 4 ? 3 : 4) : 2, (TILE != HEPT_PREC_F32 && TMAX == 4) ? 4 : 3)))
 void prep_fused_kernel(
-    const float* __restrict__ x, int ldx, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
+    const void* __restrict__ x, int ldx, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
     const float* __restrict__ wq, const float* __restrict__ wk, const float* __restrict__ wv,
     const float* __restrict__ coords, const float* __restrict__ sqrt_w, int K, const float* __restrict__ alpha,
     const int64_t* __restrict__ codes, int N, int raw_size, int T, int t0, int Tl, void* __restrict__ qhat_,
@@ -570,35 +583,42 @@ void prep_fused_kernel(
     __syncthreads();
     const FusedIn fin{ln_w, ln_b, w_s, eps, ldx};
     if (role == 0)
-        prep_role<D, C, TILE, 0, TMAX, true>(x, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(qhat_),
+        prep_role<D, C, TILE, 0, TMAX, true, IN>(x, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(qhat_),
                                        qproj, red_s, tile_s, minmax, blockIdx.x, cmax_s, fin);
     else if (role == 1)
-        prep_role<D, C, TILE, 1, TMAX, true>(x, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_),
+        prep_role<D, C, TILE, 1, TMAX, true, IN>(x, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_),
                                        kproj, red_s, tile_s, minmax, PREP_SLOTS_PER_ROLE + blockIdx.x, cmax_s, fin);
     else
-        prep_role<D, C, TILE, 2, TMAX, true>(x, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_),
+        prep_role<D, C, TILE, 2, TMAX, true, IN>(x, coords, sw_s, alpha_s, codes, N, raw_size, t0, Tl, reinterpret_cast<char*>(kvhat_),
                                        nullptr, red_s, tile_s, minmax, 0, cmax_s, fin);
 }
 
 template <int C>
-int launch_prep_fused(const float* x, int ldx, const float* ln_w, const float* ln_b, float eps, const float* wq, const float* wk,
+int launch_prep_fused(const void* x, int io_dtype, int ldx, const float* ln_w, const float* ln_b, float eps, const float* wq, const float* wk,
                       const float* wv, const float* coords, const float* sqrt_w, int K, const float* alpha,
                       const int64_t* codes, int N, int raw_size, int T, int t0, int Tl, int precision, void* qhat,
                       void* kvhat, float* qproj, float* kproj, float* minmax, hipStream_t st, ZeroJob zero) {
     const dim3 grid(prep_wgs(N), 3);
     // table slots of the kernel (accumulators, alpha slab): 4 for the usual 1-4 tables per call, else HEPT_MAX_TABLES
-#define HEPT_FUSED_LAUNCH(TILE, TMAX)                                                                                  \
-    hipLaunchKernelGGL((prep_fused_kernel<C, TILE, TMAX>), grid, dim3(PREP_THREADS), 0, st, x, ldx, ln_w, ln_b, eps, wq, \
+#define HEPT_FUSED_LAUNCH(TILE, TMAX, IN)                                                                              \
+    hipLaunchKernelGGL((prep_fused_kernel<C, TILE, TMAX, IN>), grid, dim3(PREP_THREADS), 0, st, x, ldx, ln_w, ln_b, eps, wq, \
                        wk, wv, coords, sqrt_w, K, alpha, codes, N, raw_size, T, t0, Tl, qhat, kvhat, qproj, kproj, minmax, zero)
+#define HEPT_FUSED_IN(TILE, TMAX)                                                                                      \
+    do {                                                                                                               \
+        if (io_dtype == HEPT_IN_BF16) HEPT_FUSED_LAUNCH(TILE, TMAX, HEPT_IN_BF16);                                     \
+        else if (io_dtype == HEPT_IN_F16) HEPT_FUSED_LAUNCH(TILE, TMAX, HEPT_IN_F16);                                  \
+        else HEPT_FUSED_LAUNCH(TILE, TMAX, HEPT_IN_F32);                                                               \
+    } while (0)
 #define HEPT_FUSED_TILE(TILE)                                                                                          \
     do {                                                                                                               \
-        if (Tl <= 4) HEPT_FUSED_LAUNCH(TILE, 4);                                                                       \
-        else HEPT_FUSED_LAUNCH(TILE, HEPT_MAX_TABLES);                                                                 \
+        if (Tl <= 4) HEPT_FUSED_IN(TILE, 4);                                                                           \
+        else HEPT_FUSED_IN(TILE, HEPT_MAX_TABLES);                                                                     \
     } while (0)
     if (precision == HEPT_PREC_BF16) HEPT_FUSED_TILE(HEPT_PREC_BF16);
     else if (precision == HEPT_PREC_MIXED16) HEPT_FUSED_TILE(HEPT_PREC_MIXED16);
     else HEPT_FUSED_TILE(HEPT_PREC_F32);
 #undef HEPT_FUSED_TILE
+#undef HEPT_FUSED_IN
 #undef HEPT_FUSED_LAUNCH
     return hept_launch_status();
 }
@@ -872,9 +892,10 @@ extern "C" int hept_prep_hash_in(const void* q, const void* k, const void* v, in
 }
 
 // internal (common.h): K as in hept_prep_hash_rpe
-// ldx: row pitch of x in floats (row n starts at x + n * ldx; D for contiguous rows).  The rows are read as 16-B pieces:
-// ldx is a multiple of 4 and x 16-B aligned, HEPT_ERR_SHAPE / HEPT_ERR_ARG otherwise.
-int hept_prep_hash_fused_rpe(const float* x, int ldx, const float* norm_w, const float* norm_b, float eps, const float* w_q,
+// x: rows of element type io_dtype (HEPT_IN_*).  ldx: row pitch of x in elements of that type (row n starts at element
+// n * ldx; D for contiguous rows).  The rows are read as 16-B pieces: ldx is a multiple of 4 (f32) or 8 (16-bit) and x
+// 16-B aligned, HEPT_ERR_SHAPE / HEPT_ERR_ARG otherwise.
+int hept_prep_hash_fused_rpe(const void* x, int io_dtype, int ldx, const float* norm_w, const float* norm_b, float eps, const float* w_q,
                              const float* w_k, const float* w_v, const float* coords, const float* sqrt_w, int K,
                              const float* alpha, const int64_t* codes, int N, int raw_size, int H, int D, int C, int T,
                              int t0, int Tl, int precision, void* qhat, void* kvhat, float* qproj, float* kproj,
@@ -886,16 +907,19 @@ int hept_prep_hash_fused_rpe(const float* x, int ldx, const float* norm_w, const
     if (!x || !norm_w || !norm_b || !w_q || !w_k || !w_v || !coords || !sqrt_w || !alpha || !qhat || !kvhat ||
         !qproj || !kproj || !minmax)
         return HEPT_ERR_ARG;
+    if (io_dtype != HEPT_IN_F32 && io_dtype != HEPT_IN_BF16 && io_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
+    const bool io16 = io_dtype != HEPT_IN_F32;
     if (H != 8 || D != 24 || N < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
-    if (ldx < D || ldx % 4 != 0) return HEPT_ERR_SHAPE;
-    if (ldx != D && (reinterpret_cast<uintptr_t>(x) & 15)) return HEPT_ERR_ARG;   // (contiguous rows: the contract is unchanged)
+    if (ldx < D || ldx % (io16 ? 8 : 4) != 0) return HEPT_ERR_SHAPE;
+    // (contiguous f32 rows: the contract is unchanged; 16-bit rows are refused at any pitch)
+    if ((ldx != D || io16) && (reinterpret_cast<uintptr_t>(x) & 15)) return HEPT_ERR_ARG;
     if (precision == HEPT_PREC_F32_MFMA || precision == HEPT_PREC_F32_DIFF) precision = HEPT_PREC_F32;  // same f32 tile rows, another block_attn kernel
     if (precision != HEPT_PREC_F32 && precision != HEPT_PREC_BF16 && precision != HEPT_PREC_MIXED16)
         return HEPT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
 #define HEPT_FUSED_CASE(CC)                                                                                         \
     if (C == CC)                                                                                                    \
-        return launch_prep_fused<CC>(x, ldx, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, K, alpha, codes, N, raw_size, \
+        return launch_prep_fused<CC>(x, io_dtype, ldx, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, K, alpha, codes, N, raw_size, \
                                      T, t0, Tl, precision, qhat, kvhat, qproj, kproj, minmax, st, zero);
     HEPT_FUSED_CASE(6)
     HEPT_FUSED_CASE(4)
@@ -904,11 +928,22 @@ int hept_prep_hash_fused_rpe(const float* x, int ldx, const float* norm_w, const
     return HEPT_ERR_SHAPE;
 }
 
+extern "C" int hept_prep_hash_fused_in(const void* x, int io_dtype, const float* norm_w, const float* norm_b, float eps,
+                                       const float* w_q, const float* w_k, const float* w_v, const float* coords,
+                                       const float* sqrt_w, const float* alpha, const int64_t* codes, int N,
+                                       int raw_size, int H, int D, int C, int T, int t0, int Tl, int precision,
+                                       void* qhat, void* kvhat, float* qproj, float* kproj, float* minmax,
+                                       void* stream) {
+    return hept_prep_hash_fused_rpe(x, io_dtype, D, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, 0, alpha, codes, N,
+                                    raw_size, H, D, C, T, t0, Tl, precision, qhat, kvhat, qproj, kproj, minmax, stream,
+                                    nullptr, 0);
+}
+
 extern "C" int hept_prep_hash_fused(const float* x, const float* norm_w, const float* norm_b, float eps,
                                     const float* w_q, const float* w_k, const float* w_v, const float* coords,
                                     const float* sqrt_w, const float* alpha, const int64_t* codes, int N, int raw_size,
                                     int H, int D, int C, int T, int t0, int Tl, int precision, void* qhat,
                                     void* kvhat, float* qproj, float* kproj, float* minmax, void* stream) {
-    return hept_prep_hash_fused_rpe(x, D, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, 0, alpha, codes, N, raw_size, H,
+    return hept_prep_hash_fused_rpe(x, HEPT_IN_F32, D, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, 0, alpha, codes, N, raw_size, H,
                                     D, C, T, t0, Tl, precision, qhat, kvhat, qproj, kproj, minmax, stream, nullptr, 0);
 }

@@ -7,6 +7,8 @@ operator becomes ONE node of the captured graph instead of a graph break.  ``HEP
 routes through these ops only while a compiler is tracing; eager calls keep the direct path.
 There is no CPU kernel behind any of them.  ``q``, ``k``, ``v`` of ``forward`` / ``forward_src`` may be float32,
 bfloat16 or float16 (one dtype for the three): they reach ``ops`` un-widened, and the result is float32 either way.
+``x`` of ``attn_block`` / ``attn_block_src`` may be any of the same three types as well; the block answers in the type of
+``x`` (the float32 result rounded once inside the kernel), and so do the fake kernels.
 """
 from __future__ import annotations
 
@@ -69,7 +71,7 @@ def attn_block_op(x: torch.Tensor, coords: torch.Tensor, codes: torch.Tensor, no
 @attn_block_op.register_fake
 def _(x, coords, codes, norm1_w, norm1_b, w_q, w_k, w_v, w_rpe, alpha, out_w, out_b, norm2_w, norm2_b, ff1_w, ff1_b,
       ff2_w, ff2_b, num_heads, block_size, w_per_dist, eps1, eps2, precision):
-    return x.new_empty(x.shape, dtype=torch.float32)
+    return x.new_empty(x.shape, dtype=x.dtype if x.dtype in (torch.bfloat16, torch.float16) else torch.float32)
 
 
 @torch.library.custom_op("hept_amd::attn_block_src", mutates_args=(), device_types="cuda")
@@ -91,4 +93,4 @@ def attn_block_src_op(x: torch.Tensor, coords: torch.Tensor, eta_idx: torch.Tens
 @attn_block_src_op.register_fake
 def _(x, coords, eta_idx, phi_idx, regions_h, raw_size, norm1_w, norm1_b, w_q, w_k, w_v, w_rpe, alpha, out_w, out_b,
       norm2_w, norm2_b, ff1_w, ff1_b, ff2_w, ff2_b, num_heads, block_size, w_per_dist, eps1, eps2, precision):
-    return x.new_empty(x.shape, dtype=torch.float32)
+    return x.new_empty(x.shape, dtype=x.dtype if x.dtype in (torch.bfloat16, torch.float16) else torch.float32)

@@ -98,7 +98,7 @@ def _inc(t: torch.Tensor, name: str) -> torch.Tensor:
     if not t.is_cuda:
         raise RuntimeError(f"{name} must live on the GPU (hept_amd has no CPU path); got device {t.device}")
     if t.dtype not in _IN_CODE:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+        raise TypeError(f"{name} must be float32, bfloat16 or float16, got {t.dtype}")
     t = t.contiguous()
     # (the tuned row builder fetches 16-byte pieces of 16-bit rows as well: the same repair as _f32c)
     return t.clone() if t.data_ptr() % 16 else t
@@ -548,8 +548,9 @@ def prep_hash_fused(x, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, alpha
     """``prep_hash`` with LayerNorm and the q/k/v projections fused in: ``x`` is the (N, D) input of the Attn block
     (reference ``example/transformer.py:155-156``); same outputs as :func:`prep_hash`."""
     lib = _lib.load()
-    x, norm_w, norm_b, w_q, w_k, w_v, coords, sqrt_w, alpha = (
-        _f32c(t_, nm) for t_, nm in ((x, "x"), (norm_w, "norm1.weight"), (norm_b, "norm1.bias"), (w_q, "w_q.weight"),
+    x = _inc(x, "x")   # float32, bfloat16 or float16 rows, read in place
+    norm_w, norm_b, w_q, w_k, w_v, coords, sqrt_w, alpha = (
+        _f32c(t_, nm) for t_, nm in ((norm_w, "norm1.weight"), (norm_b, "norm1.bias"), (w_q, "w_q.weight"),
                                      (w_k, "w_k.weight"), (w_v, "w_v.weight"), (coords, "coords"),
                                      (sqrt_w, "sqrt_w"), (alpha, "e2lsh.alpha")))
     n, d = x.shape
@@ -581,11 +582,12 @@ def prep_hash_fused(x, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, alpha
     qproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
     kproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
     minmax = torch.empty(tl, h, _lib.PREP_GRID, 4, device=dev, dtype=torch.float32)
-    _lib.check(lib.hept_prep_hash_fused(x.data_ptr(), norm_w.data_ptr(), norm_b.data_ptr(), float(eps), w_q.data_ptr(),
-                                        w_k.data_ptr(), w_v.data_ptr(), coords.data_ptr(), sqrt_w.data_ptr(),
-                                        alpha.data_ptr(), codes.data_ptr() if codes is not None else None, n, raw_size,
-                                        h, d, c, t, t0, tl, prec, qhat.data_ptr(), kvhat.data_ptr(), qproj.data_ptr(),
-                                        kproj.data_ptr(), minmax.data_ptr(), _stream(x)), "hept_prep_hash_fused")
+    _lib.check(lib.hept_prep_hash_fused_in(x.data_ptr(), _IN_CODE[x.dtype], norm_w.data_ptr(), norm_b.data_ptr(),
+                                           float(eps), w_q.data_ptr(), w_k.data_ptr(), w_v.data_ptr(), coords.data_ptr(),
+                                           sqrt_w.data_ptr(), alpha.data_ptr(),
+                                           codes.data_ptr() if codes is not None else None, n, raw_size, h, d, c, t, t0,
+                                           tl, prec, qhat.data_ptr(), kvhat.data_ptr(), qproj.data_ptr(),
+                                           kproj.data_ptr(), minmax.data_ptr(), _stream(x)), "hept_prep_hash_fused_in")
     return {"qhat": qhat, "kvhat": kvhat, "qproj": qproj, "kproj": kproj, "minmax": minmax}
 
 
@@ -593,22 +595,24 @@ def prep_hash_fused(x, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, alpha
 def combine_ffn(part: torch.Tensor, head_dim: int, out_weight, out_bias, x, norm_w, norm_b, eps, ff1_w, ff1_b, ff2_w,
                 ff2_b, n0: int = 0, n_count: Optional[int] = None) -> torch.Tensor:
     """``combine_out`` followed by the rest of the Attn block (residual, norm2, feed-forward, residual) in the
-    same kernel; reference ``example/transformer.py:161-165`` in eval mode.  ``x`` is the full (N, D) block input."""
+    same kernel; reference ``example/transformer.py:161-165`` in eval mode.  ``x`` is the full (N, D) block input, float32,
+    bfloat16 or float16; the result has its dtype (the float32 result rounded once, as ``.to(x.dtype)`` rounds)."""
     lib = _lib.load()
     if part.dim() == 3:
         part = part.unsqueeze(0)
     tl, n, h, _ = part.shape
     n_count = n - n0 if n_count is None else n_count
-    ts = [_f32c(t_, nm) for t_, nm in ((out_weight, "out_linear.weight"), (x, "x"), (norm_w, "norm2.weight"),
+    x = _inc(x, "x")
+    ts = [_f32c(t_, nm) for t_, nm in ((out_weight, "out_linear.weight"), (norm_w, "norm2.weight"),
                                        (norm_b, "norm2.bias"), (ff1_w, "ff.0.weight"), (ff1_b, "ff.0.bias"),
                                        (ff2_w, "ff.2.weight"), (ff2_b, "ff.2.bias"))]
-    ow, x, nw, nb, w1, b1, w2, b2 = ts
+    ow, nw, nb, w1, b1, w2, b2 = ts
     ob = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
-    y = torch.empty(n_count, head_dim, device=part.device, dtype=torch.float32)
-    _lib.check(lib.hept_combine_ffn(part.data_ptr(), _part_prec(part), tl, n, h, head_dim, n0, n_count, ow.data_ptr(),
-                                    ob.data_ptr() if ob is not None else None, x[n0:].data_ptr(), nw.data_ptr(),
-                                    nb.data_ptr(), float(eps), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                    b2.data_ptr(), y.data_ptr(), _stream(part)), "hept_combine_ffn")
+    y = torch.empty(n_count, head_dim, device=part.device, dtype=x.dtype)
+    _lib.check(lib.hept_combine_ffn_io(part.data_ptr(), _part_prec(part), tl, n, h, head_dim, n0, n_count, ow.data_ptr(),
+                                       ob.data_ptr() if ob is not None else None, x[n0:].data_ptr(), _IN_CODE[x.dtype],
+                                       nw.data_ptr(), nb.data_ptr(), float(eps), w1.data_ptr(), b1.data_ptr(),
+                                       w2.data_ptr(), b2.data_ptr(), y.data_ptr(), _stream(part)), "hept_combine_ffn_io")
     return y
 
 
@@ -643,7 +647,7 @@ def _block_args(x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2
     """Checks and marshalling shared by the two one-call blocks: (x, coords, params struct, sizes, prec, workspace,
     the tensors the struct points into)."""
     lib = _lib.load()
-    x = _f32c(x, "x")
+    x = _inc(x, "x")   # float32, bfloat16 or float16: the block reads the rows in place and answers in the same type
     coords = _f32c(coords, "coords")
     keep = {f: _f32c(params[k], k) for f, k in _BLOCK_NAMES.items()}
     n, h, d, c, t = _check_block(x.shape, coords, keep, num_heads, block_size, w_per_dist)
@@ -661,19 +665,22 @@ def attn_block_forward(x, coords, codes, params: Dict[str, torch.Tensor], *, num
                        w_per_dist: int, eps1: float = 1e-5, eps2: float = 1e-5, precision="fp32",
                        workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The whole Attn block (reference ``example/transformer.py:154-165``, eval mode) in one C call.
-    ``params`` holds the block's tensors under the reference's state-dict names."""
+    ``params`` holds the block's tensors under the reference's state-dict names.  ``x`` is float32, bfloat16 or float16
+    and the result has its dtype: 16-bit rows are widened where the kernels load them and the float32 result is rounded
+    once where it is stored -- bit for bit ``attn_block_forward(x.float(), ...).to(x.dtype)`` without the two casts."""
     lib = _lib.load()
     x, coords, st, (n, h, d, c, t), prec, workspace, _keep = _block_args(
         x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace)
     if codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n):
         raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}")
     codes = codes.contiguous()
-    y = torch.empty(n, d, device=x.device, dtype=torch.float32)
+    y = torch.empty(n, d, device=x.device, dtype=x.dtype)
     import ctypes
 
-    _lib.check(lib.hept_attn_block_forward(x.data_ptr(), coords.data_ptr(), codes.data_ptr(), ctypes.byref(st), n, h,
-                                           d, c, w_per_dist, t, block_size, prec, workspace.data_ptr(),
-                                           workspace.numel(), y.data_ptr(), _stream(x)), "hept_attn_block_forward")
+    _lib.check(lib.hept_attn_block_forward_io(x.data_ptr(), _IN_CODE[x.dtype], coords.data_ptr(), codes.data_ptr(),
+                                              ctypes.byref(st), n, h, d, c, w_per_dist, t, block_size, prec,
+                                              workspace.data_ptr(), workspace.numel(), y.data_ptr(), _stream(x)),
+               "hept_attn_block_forward_io")
     return y
 
 
@@ -682,7 +689,8 @@ def attn_block_forward_src(x, coords, region_indices, regions_h, raw_size: int, 
                            num_heads: int, block_size: int, w_per_dist: int, eps1: float = 1e-5, eps2: float = 1e-5,
                            precision="fp32", workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The src variant's Attn block (reference ``src/models/baselines/transformer.py:205-214`` with
-    ``attn_type="hept"``, eval mode) in one C call; the operator's kwargs as built by ``prepare_input_src``."""
+    ``attn_type="hept"``, eval mode) in one C call; the operator's kwargs as built by ``prepare_input_src``.  ``x`` and the
+    result: float32, bfloat16 or float16, as for :func:`attn_block_forward`."""
     lib = _lib.load()
     x, coords, st, (n, h, d, c, t), prec, workspace, _keep = _block_args(
         x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace)
@@ -690,13 +698,14 @@ def attn_block_forward_src(x, coords, region_indices, regions_h, raw_size: int, 
     raw_size = int(raw_size)
     if not 0 <= raw_size <= n:
         raise ValueError(f"raw_size must lie in [0, {n}], got {raw_size}")
-    y = torch.empty(n, d, device=x.device, dtype=torch.float32)
+    y = torch.empty(n, d, device=x.device, dtype=x.dtype)
     import ctypes
 
-    _lib.check(lib.hept_attn_block_forward_src(x.data_ptr(), coords.data_ptr(), eta.data_ptr(), phi.data_ptr(),
-                                               cfac.data_ptr(), raw_size, ctypes.byref(st), n, h, d, c, w_per_dist, t,
-                                               block_size, prec, workspace.data_ptr(), workspace.numel(), y.data_ptr(),
-                                               _stream(x)), "hept_attn_block_forward_src")
+    _lib.check(lib.hept_attn_block_forward_src_io(x.data_ptr(), _IN_CODE[x.dtype], coords.data_ptr(), eta.data_ptr(),
+                                                  phi.data_ptr(), cfac.data_ptr(), raw_size, ctypes.byref(st), n, h, d,
+                                                  c, w_per_dist, t, block_size, prec, workspace.data_ptr(),
+                                                  workspace.numel(), y.data_ptr(), _stream(x)),
+               "hept_attn_block_forward_src_io")
     return y
 
 

@@ -199,8 +199,9 @@ int hept_forward_partial(const float* q, const float* k, const float* v, const f
  * (HEPT_IN_*; HEPT_IN_F32 is exactly the entry point without the suffix).  16-bit q, k, v are contiguous (N, H*D);
  * their base is 16-byte aligned on the shapes that take the tuned row builder (H == 8 with the shipped (D, C) pairs:
  * a tile of 8 points is fetched as 16-byte pieces of 8 elements) and 2-byte aligned on every other shape;
- * HEPT_ERR_ARG otherwise, and for an unknown in_dtype.  The sharded calls, hept_partial_begin* and the Attn block take
- * f32 only. */
+ * HEPT_ERR_ARG otherwise, and for an unknown in_dtype.  The sharded calls, hept_partial_begin* and the layer stack
+ * (hept_attn_stack_forward*) take f32 only; the Attn block has its own 16-bit entry points, the *_io / hept_prep_hash_fused_in
+ * calls below, which read x AND write y in one such type. */
 int hept_prep_hash_in(const void* q, const void* k, const void* v, int in_dtype, const float* coords,
                       const float* sqrt_w, const float* alpha, const int64_t* codes,
                       int N, int raw_size, int H, int D, int C, int T, int t0, int Tl, int precision,
@@ -392,6 +393,39 @@ int hept_attn_block_forward_src(const float* x, const float* coords, const float
                                 const float* cfac, int raw_size, const hept_attn_params* params, int N, int H,
                                 int D, int C, int K, int T, int B, int precision, void* workspace,
                                 size_t workspace_bytes, float* y, void* stream);
+
+/* The block on bf16 / fp16 activations (what torch.autocast hands it behind the encoder's nn.Linear).  io_dtype
+ * (HEPT_IN_*) is the element type of the block input x AND of its output y -- one type for both; HEPT_IN_F32 is exactly
+ * the entry point without the suffix, which forwards here.  Every argument other than x, io_dtype (inserted directly
+ * after x) and y keeps its place.  Semantics for a 16-bit type, bit for bit (signed zeros included):
+ *     block_io(x16) == convert(block(widen(x16)))
+ * every bf16 / fp16 value is an f32 value, so the kernels widen the rows where they load them (row builder: three 16-byte
+ * pieces per 48-byte row instead of six; combine epilogue: the same), everything in between is the f32 code --
+ * LayerNorm, projections, hashes, rows, sort, attention, combine, residual, norm2, feed-forward -- and the f32 result is
+ * rounded ONCE where it is stored: to nearest even, fp16 overflow to +-inf (not saturating), fp16 results below 2^-14 to
+ * subnormals.  Parameters, coords and the workspace stay f32; `precision` (the tile format) is independent of io_dtype.
+ * 16-bit x and y are contiguous (N, D) with 16-byte aligned bases (for hept_combine_ffn_io: the pointers at row n0);
+ * HEPT_ERR_ARG otherwise and for an unknown io_dtype, before any launch; the shape refusals are those of the f32 calls.
+ * Not covered: hept_attn_stack_forward* (its buffer keeps f32 activations BETWEEN the layers and is rounded by the
+ * caller once at the end; a 16-bit buffer would round after every layer), the training path, the sharded calls, and
+ * x / y of two different types. */
+int hept_prep_hash_fused_in(const void* x, int io_dtype, const float* norm_w, const float* norm_b, float eps,
+                            const float* w_q, const float* w_k, const float* w_v, const float* coords,
+                            const float* sqrt_w, const float* alpha, const int64_t* codes,
+                            int N, int raw_size, int H, int D, int C, int T, int t0, int Tl, int precision,
+                            void* qhat, void* kvhat, float* qproj, float* kproj, float* minmax, void* stream);
+int hept_combine_ffn_io(const float* part, int part_precision, int Tl, int N, int H, int D, int n0, int n_count,
+                        const float* out_weight, const float* out_bias, const void* x, int io_dtype,
+                        const float* norm_w, const float* norm_b, float eps,
+                        const float* ff1_w, const float* ff1_b, const float* ff2_w, const float* ff2_b,
+                        void* y, void* stream);
+int hept_attn_block_forward_io(const void* x, int io_dtype, const float* coords, const int64_t* codes,
+                               const hept_attn_params* params, int N, int H, int D, int C, int K, int T, int B,
+                               int precision, void* workspace, size_t workspace_bytes, void* y, void* stream);
+int hept_attn_block_forward_src_io(const void* x, int io_dtype, const float* coords, const float* eta_idx,
+                                   const float* phi_idx, const float* cfac, int raw_size,
+                                   const hept_attn_params* params, int N, int H, int D, int C, int K, int T, int B,
+                                   int precision, void* workspace, size_t workspace_bytes, void* y, void* stream);
 
 /* The model's layer loop (example/transformer.py:119-121, src/models/baselines/transformer.py:133-144: n_layers Attn
  * blocks in a row, every output kept, torch.cat(all_encoded_x, dim=-1) fed to W) in one call, D == 24.
