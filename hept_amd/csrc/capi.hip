@@ -26,7 +26,7 @@ struct Workspace {
 inline int chunk_tables(int Tl) { return Tl < HEPT_MAX_TABLES ? Tl : HEPT_MAX_TABLES; }
 
 Workspace carve(void* base, int N, int H, int C, int Tl, int precision) {
-    const size_t esz = (precision == HEPT_PREC_F32 || precision == HEPT_PREC_F32_MFMA || precision == HEPT_PREC_F32_DIFF) ? 4 : 2;
+    const size_t esz = hept_f32_rows(precision) ? 4 : 2;
     const int Tc = chunk_tables(Tl);
     char* p = reinterpret_cast<char*>(base);
     size_t off = 0;
@@ -103,63 +103,78 @@ inline bool row_riders_off() {
 // profiles/r05_experiments.txt)
 static inline bool direct_v_pays(int B) { return B > 128; }
 
-// everything before the block attention, for tables [t0, t0 + Tl): parameter math, augmented rows + hashes, sort.
-// Leaves qhat / kvhat and the permutations (w.pos: q then k, (Tl, H, N) each) in the workspace.
-// q, k, v: element type in_dtype (HEPT_IN_*); 16-bit rows are widened in registers by the row builder and the riders
-int run_begin(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
-              const GeoShift& geo, const float* w_rpe, const float* alpha, int N, int H, int D, int C, int K, int T,
-              int t0, int Tl, int precision, const Workspace& w, void* stream, VSrc* dv = nullptr) {
+// The sizes of one call: tables [t0, t0 + Tl) of the T the hash parameters hold (the unsharded entries: 0 and T).  Filled
+// once by the extern "C" function and passed down by reference: ten adjacent int arguments transpose silently.
+struct Sizes {
+    int N, H, D, C, K, T, t0, Tl, B, precision;
+};
+
+// The operator's inputs.  q, k, v: element type in_dtype (HEPT_IN_*); 16-bit rows are widened in registers by the row
+// builder and the riders.  codes: the example variant's AND codes, null with a `geo`.
+struct Inputs {
+    const void *q, *k, *v;
+    int in_dtype;
+    const float* coords;
+    const int64_t* codes;
+    GeoShift geo;
+    const float *w_rpe, *alpha;
+};
+
+// The src variant's key arguments as a GeoShift, refused as every *_src entry point refuses them: nulls, then raw_size
+int geo_shift(const float* eta_idx, const float* phi_idx, const float* cfac, int raw_size, int N, GeoShift* geo) {
+    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
+    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
+    *geo = GeoShift{eta_idx, phi_idx, cfac, raw_size};
+    return HEPT_OK;
+}
+
+// Opens a call.  The order of the refusals is part of the ABI (a call with two faults answers for the first): null
+// pointers (`pointers`: the entry point's required ones are all set), the element type, the sizes, the table range,
+// `then` (the outcome of the entry point's own size checks, computed from its arguments alone), the workspace size.
+int open_call(bool pointers, int dtype, const Sizes& s, int then, void* workspace, size_t workspace_bytes, Workspace* w) {
+    if (!pointers) return HEPT_ERR_ARG;
+    if (dtype != HEPT_IN_F32 && dtype != HEPT_IN_BF16 && dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
+    const int rc = hept_check_shape(s.N, s.H, s.D, s.C, s.Tl, s.B);
+    if (rc) return rc;
+    if (s.t0 < 0 || s.t0 + s.Tl > s.T) return HEPT_ERR_SHAPE;
+    if (then) return then;
+    *w = carve(workspace, s.N, s.H, s.C, s.Tl, s.precision);
+    return workspace_bytes < w->bytes ? HEPT_ERR_ARG : HEPT_OK;
+}
+
+// `then` of the calls that hand out table sums: as f32 rows, or in the format the block attention writes them
+inline int acc_check(int acc_precision, const Sizes& s) {
+    const bool ok = acc_precision == HEPT_PREC_F32 || acc_precision == hept_part_precision(s.precision, s.D);
+    return ok ? HEPT_OK : HEPT_ERR_SHAPE;
+}
+
+// The walk over tables [s.t0, s.t0 + s.Tl) in chunks of at most HEPT_MAX_TABLES: rows + hashes, then the sort, chunk by
+// chunk; leaves the permutations (w.pos: q then k, (Tl, H, N) each) in the workspace.  `build_rows(first table, table
+// count, zero pointer, zero bytes)` launches the caller's row builder for one chunk (every chunk rewrites the rows
+// identically) and returns its code; `rows`: the v rows that ride in the sort's bucket launch, or null.
+template <class BuildRows>
+int walk_tables(const Sizes& s, const int64_t* codes, const GeoShift& geo, const Workspace& w, const HeptRowsJob* rows,
+                void* stream, BuildRows build_rows) {
     hipStream_t st = (hipStream_t)stream;
-    prof_mark(0, st);
-    // K > 0: `w_rpe` is w_rpe.weight and the row builder computes sqrt_w (H, C) from it in its prologue, every call
-    // (reference example/hept.py:22-25; nothing is cached, so an in-place update of the parameter is always seen);
-    // K == 0: the caller passes sqrt_w itself (hept_rpe_scale)
-    int rc = HEPT_OK;
+    const int N = s.N, H = s.H, Tl = s.Tl;
     int32_t* qpos = w.pos;
     int32_t* kpos = w.pos + (size_t)Tl * H * N;
-    // The v half of the kvhat rows does not depend on anything this call computes: when the sort has a bucket-sort launch
-    // (segments longer than the one-workgroup sort) that launch -- a latency-bound chain that leaves the memory system
-    // idle -- carries it as rider workgroups, and the row builder runs its q and k roles only (sort_tables.hip: RowsJob)
-    const int raw_size = geo.eta ? geo.raw_size : N;
-    // ... unless the launch is too short to hide them: with ONE local table (BASELINE config 4: one table per GPU) and
-    // 16-bit rows the bucket sort is ~12 us of its own work against ~20 us of riders -- the row builder keeps its v
-    // role there (tracking-60k, T = 1: 111.0 -> 104.7 us per forward; two tables and more, and f32 rows at any count,
-    // are faster with riders: profiles/r04_experiments.txt)
-    const bool f32_rows = precision == HEPT_PREC_F32 || precision == HEPT_PREC_F32_MFMA || precision == HEPT_PREC_F32_DIFF;
-    // (HEPT_FORCE_ROW_RIDERS=1: riders at any table count -- A/B measurements; read once)
-    static const bool force_ride = [] { const char* e = getenv("HEPT_FORCE_ROW_RIDERS"); return e && *e && *e != '0'; }();
-    // f32 rows, round 5: nobody builds the v half at all when the caller of run_begin runs the block attention itself
-    // (`dv`): the split-bf16 kernel stages its value planes from the caller's v rows (96 of 128 fetched bytes used, the
-    // same sectors as a padded kvhat row) and the bucket sort loses its riders -- 46 MB read + 61.5 MB written per call
-    // at tracking-60k (HEPT_NO_DIRECT_V=1: A/B measurements; read once)
-    static const bool no_direct_v = [] { const char* e = getenv("HEPT_NO_DIRECT_V"); return e && *e && *e != '0'; }();
-    // (the split kernel reads f32 pieces of v: 16-bit inputs get their value rows from the riders or the v role)
-    const bool direct_v = dv && precision == HEPT_PREC_F32 && D % 4 == 0 && !no_direct_v && in_dtype == HEPT_IN_F32 &&
-                          (reinterpret_cast<uintptr_t>(v) & 15) == 0;
-    if (dv) *dv = direct_v ? VSrc{reinterpret_cast<const float*>(v), raw_size} : VSrc{};
-    // (the riders fetch 16-bit rows as 8-byte pieces; a base the generic row builder accepts at 2 bytes keeps the v role)
-    const bool ride_base = in_dtype == HEPT_IN_F32 || (reinterpret_cast<uintptr_t>(v) & 7) == 0;
-    const bool ride = !direct_v && ride_base && Tl <= HEPT_MAX_TABLES && (Tl >= 2 || f32_rows || force_ride) && hept_sort_carries_rows(N, H, D) && !row_riders_off();
-    const HeptRowsJob job{v, w.kvhat, N, raw_size, H, D, precision, in_dtype};
-    const HeptRowsJob* rows = ride ? &job : nullptr;
-    for (int c0 = 0; c0 < Tl; c0 += HEPT_MAX_TABLES) {   // chunks of tables (the rows are rewritten identically)
+    for (int c0 = 0; c0 < Tl; c0 += HEPT_MAX_TABLES) {
         const int tc = Tl - c0 < HEPT_MAX_TABLES ? Tl - c0 : HEPT_MAX_TABLES;
         // (the row builder also clears the sort's bucket counters on its way: no fill launch in front of the sort)
         void* zptr = nullptr;
         size_t zbytes = 0;
         hept_sort_zero_block(w.sort_ws, N, H, tc, &zptr, &zbytes);
-        rc = hept_prep_hash_rpe(q, k, v, coords, w_rpe, K, alpha, codes, N, raw_size, H, D, C, T,
-                                t0 + c0, tc, precision, w.qhat, w.kvhat, w.qproj, w.kproj, w.minmax, stream,
-                                (ride || direct_v) ? 2 : 3, zptr, zbytes, in_dtype);
+        int rc = build_rows(s.t0 + c0, tc, zptr, zbytes);
         if (rc) return rc;
         if (c0 == 0) prof_mark(1, st);
         // the sort writes one (2, tc, H, N) array: straight into w.pos when the call is a single chunk
         int32_t* cq = Tl <= HEPT_MAX_TABLES ? qpos : w.pos_chunk;
         int32_t* ck = cq + (size_t)tc * H * N;
-        rc = geo.eta ? hept_sort_tables_src_rows(w.qproj, w.kproj, geo.eta, geo.phi, geo.cfac, w.minmax, N, H, T, t0 + c0,
-                                                 tc, w.sort_ws, cq, ck, rows, stream, zbytes != 0)
-                     : hept_sort_tables_rows(w.qproj, w.kproj, codes, w.minmax, N, H, T, t0 + c0, tc, w.sort_ws, cq, ck,
-                                             rows, stream, zbytes != 0);
+        rc = geo.eta ? hept_sort_tables_src_rows(w.qproj, w.kproj, geo.eta, geo.phi, geo.cfac, w.minmax, N, H, s.T,
+                                                 s.t0 + c0, tc, w.sort_ws, cq, ck, rows, stream, zbytes != 0)
+                     : hept_sort_tables_rows(w.qproj, w.kproj, codes, w.minmax, N, H, s.T, s.t0 + c0, tc, w.sort_ws, cq,
+                                             ck, rows, stream, zbytes != 0);
         if (rc) return rc;
         if (cq != qpos) {
             const size_t off = (size_t)c0 * H * N, bytes = (size_t)tc * H * N * 4;
@@ -172,16 +187,54 @@ int run_begin(const void* q, const void* k, const void* v, int in_dtype, const f
     return HEPT_OK;
 }
 
+// everything before the block attention, for tables [t0, t0 + Tl): parameter math, augmented rows + hashes, sort.
+// Leaves qhat / kvhat and the permutations in the workspace (walk_tables).
+int run_begin(const Inputs& in, const Sizes& s, const Workspace& w, void* stream, VSrc* dv = nullptr) {
+    prof_mark(0, (hipStream_t)stream);
+    // K > 0: `w_rpe` is w_rpe.weight and the row builder computes sqrt_w (H, C) from it in its prologue, every call
+    // (reference example/hept.py:22-25; nothing is cached, so an in-place update of the parameter is always seen);
+    // K == 0: the caller passes sqrt_w itself (hept_rpe_scale)
+    // The v half of the kvhat rows does not depend on anything this call computes: when the sort has a bucket-sort launch
+    // (segments longer than the one-workgroup sort) that launch -- a latency-bound chain that leaves the memory system
+    // idle -- carries it as rider workgroups, and the row builder runs its q and k roles only (sort_tables.hip: RowsJob)
+    const int raw_size = in.geo.eta ? in.geo.raw_size : s.N;
+    // ... unless the launch is too short to hide them: with ONE local table (BASELINE config 4: one table per GPU) and
+    // 16-bit rows the bucket sort is ~12 us of its own work against ~20 us of riders -- the row builder keeps its v
+    // role there (tracking-60k, T = 1: 111.0 -> 104.7 us per forward; two tables and more, and f32 rows at any count,
+    // are faster with riders: profiles/r04_experiments.txt)
+    const bool f32_rows = hept_f32_rows(s.precision);
+    // (HEPT_FORCE_ROW_RIDERS=1: riders at any table count -- A/B measurements; read once)
+    static const bool force_ride = [] { const char* e = getenv("HEPT_FORCE_ROW_RIDERS"); return e && *e && *e != '0'; }();
+    // f32 rows, round 5: nobody builds the v half at all when the caller of run_begin runs the block attention itself
+    // (`dv`): the split-bf16 kernel stages its value planes from the caller's v rows (96 of 128 fetched bytes used, the
+    // same sectors as a padded kvhat row) and the bucket sort loses its riders -- 46 MB read + 61.5 MB written per call
+    // at tracking-60k (HEPT_NO_DIRECT_V=1: A/B measurements; read once)
+    static const bool no_direct_v = [] { const char* e = getenv("HEPT_NO_DIRECT_V"); return e && *e && *e != '0'; }();
+    // (the split kernel reads f32 pieces of v: 16-bit inputs get their value rows from the riders or the v role)
+    const bool direct_v = dv && s.precision == HEPT_PREC_F32 && s.D % 4 == 0 && !no_direct_v &&
+                          in.in_dtype == HEPT_IN_F32 && (reinterpret_cast<uintptr_t>(in.v) & 15) == 0;
+    if (dv) *dv = direct_v ? VSrc{reinterpret_cast<const float*>(in.v), raw_size} : VSrc{};
+    // (the riders fetch 16-bit rows as 8-byte pieces; a base the generic row builder accepts at 2 bytes keeps the v role)
+    const bool ride_base = in.in_dtype == HEPT_IN_F32 || (reinterpret_cast<uintptr_t>(in.v) & 7) == 0;
+    const bool ride = !direct_v && ride_base && s.Tl <= HEPT_MAX_TABLES && (s.Tl >= 2 || f32_rows || force_ride) &&
+                      hept_sort_carries_rows(s.N, s.H, s.D) && !row_riders_off();
+    const HeptRowsJob job{in.v, w.kvhat, s.N, raw_size, s.H, s.D, s.precision, in.in_dtype};
+    return walk_tables(s, in.codes, in.geo, w, ride ? &job : nullptr, stream,
+                       [&](int t0, int tc, void* zptr, size_t zbytes) {
+                           return hept_prep_hash_rpe(in.q, in.k, in.v, in.coords, in.w_rpe, s.K, in.alpha, in.codes, s.N, raw_size,
+                                                     s.H, s.D, s.C, s.T, t0, tc, s.precision, w.qhat, w.kvhat, w.qproj,
+                                                     w.kproj, w.minmax, stream, (ride || direct_v) ? 2 : 3, zptr, zbytes,
+                                                     in.in_dtype);
+                       });
+}
+
 // stages shared by hept_forward / hept_forward_partial; leaves per-table partials in `part`
-int run_tables(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
-               const GeoShift& geo, const float* w_rpe, const float* alpha, int N, int H, int D, int C, int K, int T,
-               int t0, int Tl, int B, int precision, const Workspace& w, float* part, void* stream) {
+int run_tables(const Inputs& in, const Sizes& s, const Workspace& w, float* part, void* stream) {
     VSrc dv;
-    int rc = run_begin(q, k, v, in_dtype, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream,
-                       direct_v_pays(B) ? &dv : nullptr);
+    int rc = run_begin(in, s, w, stream, direct_v_pays(s.B) ? &dv : nullptr);
     if (rc) return rc;
-    rc = hept_block_attn_heads_push(w.qhat, w.kvhat, w.pos, w.pos + (size_t)Tl * H * N, N, H, D, Tl, B, precision, 0, H, H,
-                                    0, N, part, nullptr, stream, dv);
+    rc = hept_block_attn_heads_push(w.qhat, w.kvhat, w.pos, w.pos + (size_t)s.Tl * s.H * s.N, s.N, s.H, s.D, s.Tl, s.B,
+                                    s.precision, 0, s.H, s.H, 0, s.N, part, nullptr, stream, dv);
     prof_mark(3, (hipStream_t)stream);
     return rc;
 }
@@ -196,7 +249,7 @@ void hept_prof_mark_sort_mid(void* stream) {
 extern "C" int hept_abi_version(void) { return 22; }
 
 extern "C" int hept_part_precision(int precision, int D) {
-    return (precision != HEPT_PREC_F32 && precision != HEPT_PREC_F32_MFMA && precision != HEPT_PREC_F32_DIFF && D == 24) ? HEPT_PREC_BF16 : HEPT_PREC_F32;
+    return (!hept_f32_rows(precision) && D == 24) ? HEPT_PREC_BF16 : HEPT_PREC_F32;
 }
 
 extern "C" int hept_check_shape(int N, int H, int D, int C, int Tl, int B) {
@@ -215,48 +268,42 @@ extern "C" size_t hept_workspace_bytes(int N, int H, int D, int C, int Tl, int B
 }
 
 namespace {
-int forward_impl(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
-                 const GeoShift& geo, const float* w_rpe, const float* alpha, const float* out_weight,
-                 const float* out_bias, int N, int H, int D, int C, int K, int T, int B, int precision,
-                 void* workspace, size_t workspace_bytes, float* out, void* stream) {
-    if (!q || !k || !v || !coords || !w_rpe || !alpha || !out_weight || !workspace || !out) return HEPT_ERR_ARG;
-    if (in_dtype != HEPT_IN_F32 && in_dtype != HEPT_IN_BF16 && in_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
-    int rc = hept_check_shape(N, H, D, C, T, B);
+int forward_impl(const Inputs& in, const float* out_weight, const float* out_bias, const Sizes& s, void* workspace,
+                 size_t workspace_bytes, float* out, void* stream) {
+    Workspace w;
+    int rc = open_call(in.q && in.k && in.v && in.coords && in.w_rpe && in.alpha && out_weight && workspace && out,
+                       in.in_dtype, s, HEPT_OK, workspace, workspace_bytes, &w);
     if (rc) return rc;
-    const Workspace w = carve(workspace, N, H, C, T, precision);
-    if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
-    rc = run_tables(q, k, v, in_dtype, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, 0, T, B, precision, w, w.part,
-                    stream);
+    rc = run_tables(in, s, w, w.part, stream);
     if (rc) return rc;
-    rc = hept_combine_out(w.part, hept_part_precision(precision, D), T, N, H, D, 0, N, out_weight, out_bias, out,
-                          stream);
+    rc = hept_combine_out(w.part, hept_part_precision(s.precision, s.D), s.T, s.N, s.H, s.D, 0, s.N, out_weight, out_bias,
+                          out, stream);
     prof_mark(4, (hipStream_t)stream);
     prof_call_done();
     return rc;
 }
 
-int forward_partial_impl(const void* q, const void* k, const void* v, int in_dtype, const float* coords, const int64_t* codes,
-                         const GeoShift& geo, const float* w_rpe, const float* alpha, int N, int H, int D, int C,
-                         int K, int T, int t0, int Tl, int B, int precision, int acc_precision, void* workspace,
-                         size_t workspace_bytes, float* acc, void* stream) {
-    if (!q || !k || !v || !coords || !w_rpe || !alpha || !workspace || !acc) return HEPT_ERR_ARG;
-    if (in_dtype != HEPT_IN_F32 && in_dtype != HEPT_IN_BF16 && in_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
-    int rc = hept_check_shape(N, H, D, C, Tl, B);
+int forward_partial_impl(const Inputs& in, const Sizes& s, int acc_precision, void* workspace, size_t workspace_bytes,
+                         float* acc, void* stream) {
+    Workspace w;
+    int rc = open_call(in.q && in.k && in.v && in.coords && in.w_rpe && in.alpha && workspace && acc, in.in_dtype, s,
+                       acc_check(acc_precision, s), workspace, workspace_bytes, &w);
     if (rc) return rc;
-    if (t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
-    if (acc_precision != HEPT_PREC_F32 && acc_precision != hept_part_precision(precision, D)) return HEPT_ERR_SHAPE;
-    const Workspace w = carve(workspace, N, H, C, Tl, precision);
-    if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
     // one local table already in the requested row format: block_attn scatters straight into acc, no reduction pass
-    const int pprec = hept_part_precision(precision, D);
-    const bool direct = Tl == 1 && pprec == acc_precision;
-    float* part = direct ? acc : w.part;
-    rc = run_tables(q, k, v, in_dtype, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B, precision, w, part,
-                    stream);
-    if (!rc && !direct) rc = hept_reduce_tables(w.part, pprec, Tl, N, H, D, acc, acc_precision, stream);
+    const int pprec = hept_part_precision(s.precision, s.D);
+    const bool direct = s.Tl == 1 && pprec == acc_precision;
+    rc = run_tables(in, s, w, direct ? acc : w.part, stream);
+    if (!rc && !direct) rc = hept_reduce_tables(w.part, pprec, s.Tl, s.N, s.H, s.D, acc, acc_precision, stream);
     prof_mark(4, (hipStream_t)stream);
     prof_call_done();
     return rc;
+}
+
+int partial_begin_impl(const Inputs& in, const Sizes& s, void* workspace, size_t workspace_bytes, void* stream) {
+    Workspace w;
+    const int rc = open_call(in.q && in.k && in.v && in.coords && in.w_rpe && in.alpha && workspace, in.in_dtype, s, HEPT_OK,
+                             workspace, workspace_bytes, &w);
+    return rc ? rc : run_begin(in, s, w, stream);
 }
 }  // namespace
 
@@ -273,8 +320,8 @@ extern "C" int hept_forward_in(const void* q, const void* k, const void* v, int 
                                const float* out_bias, int N, int H, int D, int C, int K, int T, int B, int precision,
                                void* workspace, size_t workspace_bytes, float* out, void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return forward_impl(q, k, v, in_dtype, coords, codes, GeoShift{}, w_rpe, alpha, out_weight, out_bias, N, H, D, C, K, T,
-                        B, precision, workspace, workspace_bytes, out, stream);
+    return forward_impl(Inputs{q, k, v, in_dtype, coords, codes, GeoShift{}, w_rpe, alpha}, out_weight, out_bias,
+                        Sizes{N, H, D, C, K, T, 0, T, B, precision}, workspace, workspace_bytes, out, stream);
 }
 
 extern "C" int hept_forward_partial(const float* q, const float* k, const float* v, const float* coords,
@@ -292,8 +339,9 @@ extern "C" int hept_forward_partial_in(const void* q, const void* k, const void*
                                        int acc_precision, void* workspace, size_t workspace_bytes, float* acc,
                                        void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return forward_partial_impl(q, k, v, in_dtype, coords, codes, GeoShift{}, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B,
-                                precision, acc_precision, workspace, workspace_bytes, acc, stream);
+    return forward_partial_impl(Inputs{q, k, v, in_dtype, coords, codes, GeoShift{}, w_rpe, alpha},
+                                Sizes{N, H, D, C, K, T, t0, Tl, B, precision}, acc_precision, workspace, workspace_bytes,
+                                acc, stream);
 }
 
 extern "C" int hept_forward_src(const float* q, const float* k, const float* v, const float* coords,
@@ -310,10 +358,10 @@ extern "C" int hept_forward_src_in(const void* q, const void* k, const void* v, 
                                    const float* w_rpe, const float* alpha, const float* out_weight,
                                    const float* out_bias, int N, int H, int D, int C, int K, int T, int B,
                                    int precision, void* workspace, size_t workspace_bytes, float* out, void* stream) {
-    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
-    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return forward_impl(q, k, v, in_dtype, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe, alpha,
-                        out_weight, out_bias, N, H, D, C, K, T, B, precision, workspace, workspace_bytes, out, stream);
+    GeoShift geo;
+    if (const int rc = geo_shift(eta_idx, phi_idx, cfac, raw_size, N, &geo)) return rc;
+    return forward_impl(Inputs{q, k, v, in_dtype, coords, nullptr, geo, w_rpe, alpha}, out_weight, out_bias,
+                        Sizes{N, H, D, C, K, T, 0, T, B, precision}, workspace, workspace_bytes, out, stream);
 }
 
 extern "C" int hept_forward_partial_src(const float* q, const float* k, const float* v, const float* coords,
@@ -332,35 +380,20 @@ extern "C" int hept_forward_partial_src_in(const void* q, const void* k, const v
                                            int N, int H, int D, int C, int K, int T, int t0, int Tl, int B,
                                            int precision, int acc_precision, void* workspace, size_t workspace_bytes,
                                            float* acc, void* stream) {
-    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
-    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return forward_partial_impl(q, k, v, in_dtype, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe,
-                                alpha, N, H, D, C, K, T, t0, Tl, B, precision, acc_precision, workspace, workspace_bytes,
+    GeoShift geo;
+    if (const int rc = geo_shift(eta_idx, phi_idx, cfac, raw_size, N, &geo)) return rc;
+    return forward_partial_impl(Inputs{q, k, v, in_dtype, coords, nullptr, geo, w_rpe, alpha},
+                                Sizes{N, H, D, C, K, T, t0, Tl, B, precision}, acc_precision, workspace, workspace_bytes,
                                 acc, stream);
 }
-
-namespace {
-int partial_begin_impl(const float* q, const float* k, const float* v, const float* coords, const int64_t* codes,
-                       const GeoShift& geo, const float* w_rpe, const float* alpha, int N, int H, int D, int C, int K,
-                       int T, int t0, int Tl, int B, int precision, void* workspace, size_t workspace_bytes,
-                       void* stream) {
-    if (!q || !k || !v || !coords || !w_rpe || !alpha || !workspace) return HEPT_ERR_ARG;
-    int rc = hept_check_shape(N, H, D, C, Tl, B);
-    if (rc) return rc;
-    if (t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
-    const Workspace w = carve(workspace, N, H, C, Tl, precision);
-    if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
-    return run_begin(q, k, v, HEPT_IN_F32, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream);
-}
-}  // namespace
 
 extern "C" int hept_partial_begin(const float* q, const float* k, const float* v, const float* coords,
                                   const int64_t* codes, const float* w_rpe, const float* alpha, int N, int H, int D,
                                   int C, int K, int T, int t0, int Tl, int B, int precision, void* workspace,
                                   size_t workspace_bytes, void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return partial_begin_impl(q, k, v, coords, codes, GeoShift{}, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, B, precision,
-                              workspace, workspace_bytes, stream);
+    return partial_begin_impl(Inputs{q, k, v, HEPT_IN_F32, coords, codes, GeoShift{}, w_rpe, alpha},
+                              Sizes{N, H, D, C, K, T, t0, Tl, B, precision}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int hept_partial_begin_src(const float* q, const float* k, const float* v, const float* coords,
@@ -368,17 +401,22 @@ extern "C" int hept_partial_begin_src(const float* q, const float* k, const floa
                                       const float* w_rpe, const float* alpha, int N, int H, int D, int C, int K, int T,
                                       int t0, int Tl, int B, int precision, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
-    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return partial_begin_impl(q, k, v, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe, alpha, N, H,
-                              D, C, K, T, t0, Tl, B, precision, workspace, workspace_bytes, stream);
+    GeoShift geo;
+    if (const int rc = geo_shift(eta_idx, phi_idx, cfac, raw_size, N, &geo)) return rc;
+    return partial_begin_impl(Inputs{q, k, v, HEPT_IN_F32, coords, nullptr, geo, w_rpe, alpha},
+                              Sizes{N, H, D, C, K, T, t0, Tl, B, precision}, workspace, workspace_bytes, stream);
 }
 
-namespace {
-// block attention of heads [h0, h0 + hg) for the tables of the preceding run_begin, summed over those tables into
-// dst (n_pad, hg, row); rows [N, n_pad) are zero
-int partial_heads_impl(const Workspace& w, int N, int H, int D, int Tl, int B, int precision, int h0, int hg, int n_pad,
-                       int acc_precision, float* dst, void* stream) {
+// block attention of heads [h0, h0 + hg) for the tables of the preceding hept_partial_begin, summed over those tables
+// into dst (n_pad, hg, row); rows [N, n_pad) are zero
+extern "C" int hept_partial_heads(void* workspace, size_t workspace_bytes, int N, int H, int D, int C, int Tl, int B,
+                                  int precision, int h0, int hg, int n_pad, int acc_precision, float* dst,
+                                  void* stream) {
+    const Sizes s{N, H, D, C, 0, Tl, 0, Tl, B, precision};   // (the Tl tables of the begin call; no hash parameters here)
+    const int then = (h0 < 0 || hg < 1 || h0 + hg > H || n_pad < N) ? HEPT_ERR_SHAPE : acc_check(acc_precision, s);
+    Workspace w;
+    int rc = open_call(workspace && dst, HEPT_IN_F32, s, then, workspace, workspace_bytes, &w);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int pprec = hept_part_precision(precision, D);
     const int32_t* qpos = w.pos;
@@ -387,7 +425,6 @@ int partial_heads_impl(const Workspace& w, int N, int H, int D, int Tl, int B, i
     // dst; the padding rows are zeroed (nothing reads them, but they travel)
     const bool direct = Tl == 1 && pprec == acc_precision;
     const bool rec = g_prof.mode == 1;
-    int rc;
     if (rec) prof_mark(2, st);
     if (direct) {
         const size_t row_bytes = (size_t)hg * (acc_precision == HEPT_PREC_BF16 ? 64 : 128);
@@ -406,20 +443,6 @@ int partial_heads_impl(const Workspace& w, int N, int H, int D, int Tl, int B, i
     if (rec) prof_call_done();
     return rc;
 }
-}  // namespace
-
-extern "C" int hept_partial_heads(void* workspace, size_t workspace_bytes, int N, int H, int D, int C, int Tl, int B,
-                                  int precision, int h0, int hg, int n_pad, int acc_precision, float* dst,
-                                  void* stream) {
-    if (!workspace || !dst) return HEPT_ERR_ARG;
-    int rc = hept_check_shape(N, H, D, C, Tl, B);
-    if (rc) return rc;
-    if (h0 < 0 || hg < 1 || h0 + hg > H || n_pad < N) return HEPT_ERR_SHAPE;
-    if (acc_precision != HEPT_PREC_F32 && acc_precision != hept_part_precision(precision, D)) return HEPT_ERR_SHAPE;
-    const Workspace w = carve(workspace, N, H, C, Tl, precision);
-    if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
-    return partial_heads_impl(w, N, H, D, Tl, B, precision, h0, hg, n_pad, acc_precision, dst, stream);
-}
 
 // ---- table sharding in one call: kernels on the caller's stream, RCCL transfers of finished head groups on the
 //      communicator's side stream
@@ -431,11 +454,9 @@ extern "C" size_t hept_exchange_bytes(int N, int H, int D, int world, int precis
 }
 
 namespace {
-int sharded_steps(hept_comm* comm, const float* q, const float* k, const float* v, const float* coords,
-                  const int64_t* codes, const GeoShift& geo, const float* w_rpe, const float* alpha,
-                  const float* out_weight, const float* out_bias, int N, int H, int D, int C, int K, int T, int t0,
-                  int Tl, int B, int precision, int head_groups, bool one_sided, const Workspace& w, void* xbuf,
-                  float* out_full, void* stream) {
+int sharded_steps(hept_comm* comm, const Inputs& in, const float* out_weight, const float* out_bias, const Sizes& s,
+                  int head_groups, bool one_sided, const Workspace& w, void* xbuf, float* out_full, void* stream) {
+    const int N = s.N, H = s.H, D = s.D, Tl = s.Tl, B = s.B, precision = s.precision;
     P2pLayout lay = hept_p2p_layout(N, H, D, comm->world, precision);
     // view mode: the gathered output of step e lies in region e & 1 and is read there by the caller
     const bool view = one_sided && comm->out_view;
@@ -455,8 +476,7 @@ int sharded_steps(hept_comm* comm, const float* q, const float* k, const float* 
     char* send = reinterpret_cast<char*>(xbuf);
     char* recv = one_sided ? comm->p2p_local + lay.recv_off : send + up256((size_t)n_pad * H * row);
     VSrc dv;
-    int rc = run_begin(q, k, v, HEPT_IN_F32, coords, codes, geo, w_rpe, alpha, N, H, D, C, K, T, t0, Tl, precision, w, stream,
-                       direct_v_pays(B) ? &dv : nullptr);
+    int rc = run_begin(in, s, w, stream, direct_v_pays(B) ? &dv : nullptr);
     if (rc) return rc;
     const int pprec = hept_part_precision(precision, D);
     const bool direct = Tl == 1 && !one_sided;   // one local table: block_attn scatters straight into the send buffer
@@ -600,28 +620,25 @@ int sharded_steps(hept_comm* comm, const float* q, const float* k, const float* 
     return rc;
 }
 
-int forward_sharded_impl(hept_comm* comm, const float* q, const float* k, const float* v, const float* coords,
-                         const int64_t* codes, const GeoShift& geo, const float* w_rpe, const float* alpha,
-                         const float* out_weight, const float* out_bias, int N, int H, int D, int C, int K, int T,
-                         int t0, int Tl, int B, int precision, int head_groups, int transport, void* workspace,
-                         size_t workspace_bytes, void* xbuf, size_t xbuf_bytes, float* out_full, void* stream) {
+int forward_sharded_impl(hept_comm* comm, const Inputs& in, const float* out_weight, const float* out_bias,
+                         const Sizes& s, int head_groups, int transport, void* workspace, size_t workspace_bytes,
+                         void* xbuf, size_t xbuf_bytes, float* out_full, void* stream) {
     // Everything that can be refused is refused BEFORE the step takes its epoch: a rank that bails out here has not
     // moved, and the others time out against it once (and say so) instead of running one epoch apart for good.
-    if (!comm || !q || !k || !v || !coords || !w_rpe || !alpha || !out_weight || !workspace) return HEPT_ERR_ARG;
+    if (!comm || !in.q || !in.k || !in.v || !in.coords || !in.w_rpe || !in.alpha || !out_weight || !workspace)
+        return HEPT_ERR_ARG;
     const bool one_sided = transport == HEPT_TRANSPORT_ONE_SIDED;
     // no output pointer: the one-sided transport in view mode only (the output is read in the exchange buffer)
     if (!out_full && !(one_sided && comm->out_view)) return HEPT_ERR_ARG;
     if (!one_sided && (transport != HEPT_TRANSPORT_RCCL || !xbuf)) return HEPT_ERR_ARG;
-    int rc = hept_check_shape(N, H, D, C, Tl, B);
+    const int then = (head_groups < 1 || head_groups > HEPT_MAX_HEAD_GROUPS || s.H % head_groups != 0 || s.K < 0 ||
+                      (s.K > 0 && s.H * (s.C - 1) * s.K > 1024)) ? HEPT_ERR_SHAPE : HEPT_OK;
+    Workspace w;
+    int rc = open_call(true, in.in_dtype, s, then, workspace, workspace_bytes, &w);
     if (rc) return rc;
-    if (t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
-    if (head_groups < 1 || head_groups > HEPT_MAX_HEAD_GROUPS || H % head_groups != 0) return HEPT_ERR_SHAPE;
-    if (K < 0 || (K > 0 && H * (C - 1) * K > 1024)) return HEPT_ERR_SHAPE;
-    const Workspace w = carve(workspace, N, H, C, Tl, precision);
-    if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
-    if (!one_sided && xbuf_bytes < hept_exchange_bytes(N, H, D, comm->world, precision)) return HEPT_ERR_ARG;
+    if (!one_sided && xbuf_bytes < hept_exchange_bytes(s.N, s.H, s.D, comm->world, s.precision)) return HEPT_ERR_ARG;
     if (one_sided) {
-        const P2pLayout lay = hept_p2p_layout(N, H, D, comm->world, precision);
+        const P2pLayout lay = hept_p2p_layout(s.N, s.H, s.D, comm->world, s.precision);
         if (!comm->p2p_open || comm->p2p_bytes < lay.bytes) return HEPT_ERR_ARG;
         if (head_groups * comm->world > 256) return HEPT_ERR_SHAPE;
         // a wait of an EARLIER step timed out on this GPU (the kernel wrote the host-mapped status word; that step's
@@ -635,8 +652,7 @@ int forward_sharded_impl(hept_comm* comm, const float* q, const float* k, const 
         }
         ++comm->epoch;
     }
-    rc = sharded_steps(comm, q, k, v, coords, codes, geo, w_rpe, alpha, out_weight, out_bias, N, H, D, C, K, T, t0, Tl, B,
-                       precision, head_groups, one_sided, w, xbuf, out_full, stream);
+    rc = sharded_steps(comm, in, out_weight, out_bias, s, head_groups, one_sided, w, xbuf, out_full, stream);
     // a failure after the epoch was taken (a launch error half-way through the step): the peers will time out on this
     // step, and this rank may have raised only some of its flags -- fatal for the transport until it is reset
     if (rc && one_sided) comm->broken = true;
@@ -651,9 +667,9 @@ extern "C" int hept_forward_sharded(hept_comm* comm, const float* q, const float
                                     int transport, void* workspace, size_t workspace_bytes, void* xbuf,
                                     size_t xbuf_bytes, float* out_full, void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return forward_sharded_impl(comm, q, k, v, coords, codes, GeoShift{}, w_rpe, alpha, out_weight, out_bias, N, H, D,
-                                C, K, T, t0, Tl, B, precision, head_groups, transport, workspace, workspace_bytes, xbuf,
-                                xbuf_bytes, out_full, stream);
+    return forward_sharded_impl(comm, Inputs{q, k, v, HEPT_IN_F32, coords, codes, GeoShift{}, w_rpe, alpha}, out_weight,
+                                out_bias, Sizes{N, H, D, C, K, T, t0, Tl, B, precision}, head_groups, transport, workspace,
+                                workspace_bytes, xbuf, xbuf_bytes, out_full, stream);
 }
 
 extern "C" int hept_forward_sharded_src(hept_comm* comm, const float* q, const float* k, const float* v,
@@ -663,11 +679,11 @@ extern "C" int hept_forward_sharded_src(hept_comm* comm, const float* q, const f
                                         int K, int T, int t0, int Tl, int B, int precision, int head_groups,
                                         int transport, void* workspace, size_t workspace_bytes, void* xbuf,
                                         size_t xbuf_bytes, float* out_full, void* stream) {
-    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
-    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return forward_sharded_impl(comm, q, k, v, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, w_rpe,
-                                alpha, out_weight, out_bias, N, H, D, C, K, T, t0, Tl, B, precision, head_groups,
-                                transport, workspace, workspace_bytes, xbuf, xbuf_bytes, out_full, stream);
+    GeoShift geo;
+    if (const int rc = geo_shift(eta_idx, phi_idx, cfac, raw_size, N, &geo)) return rc;
+    return forward_sharded_impl(comm, Inputs{q, k, v, HEPT_IN_F32, coords, nullptr, geo, w_rpe, alpha}, out_weight,
+                                out_bias, Sizes{N, H, D, C, K, T, t0, Tl, B, precision}, head_groups, transport, workspace,
+                                workspace_bytes, xbuf, xbuf_bytes, out_full, stream);
 }
 
 namespace {
@@ -687,59 +703,33 @@ int attn_params_check(const hept_attn_params* p) {
 // rounded once where it is stored; everything in between is the f32 block.
 // ldx / ldy: row pitches of x and y in such elements (D, D: the contiguous (N, D) tensors of hept_attn_block_forward).
 int attn_block_impl(const void* x, int io_dtype, int ldx, const float* coords, const int64_t* codes, const GeoShift& geo,
-                    const hept_attn_params* p, int N, int H, int D, int C, int K, int T, int B, int precision,
-                    void* workspace, size_t workspace_bytes, void* y, int ldy, void* stream) {
-    if (!x || !coords || !p || !workspace || !y) return HEPT_ERR_ARG;
-    int rc = attn_params_check(p);
-    if (rc) return rc;
-    if (io_dtype != HEPT_IN_F32 && io_dtype != HEPT_IN_BF16 && io_dtype != HEPT_IN_F16) return HEPT_ERR_ARG;
+                    const hept_attn_params* p, const Sizes& s, void* workspace, size_t workspace_bytes, void* y, int ldy,
+                    void* stream) {
     // 16-bit rows move as 16-B (x) and 8-B (y) pieces: refused here, before the row builder has run for nothing
-    if (io_dtype != HEPT_IN_F32 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
-        return HEPT_ERR_ARG;
-    rc = hept_check_shape(N, H, D, C, T, B);
+    const bool aligned =
+        io_dtype == HEPT_IN_F32 || !((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15);
+    Workspace w;
+    int rc = open_call(x && coords && p && workspace && y && !attn_params_check(p) && aligned, io_dtype, s,
+                       s.D != 24 ? HEPT_ERR_SHAPE : HEPT_OK, workspace, workspace_bytes, &w);
     if (rc) return rc;
-    if (D != 24) return HEPT_ERR_SHAPE;
-    const Workspace w = carve(workspace, N, H, C, T, precision);
-    if (workspace_bytes < w.bytes) return HEPT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     prof_mark(0, st);
-    const int raw_size = geo.eta ? geo.raw_size : N;
-    int32_t* qpos = w.pos;
-    int32_t* kpos = w.pos + (size_t)T * H * N;
-    // any number of tables: the row builder and the sort walk chunks of HEPT_MAX_TABLES, as run_begin does (the rows
-    // are rewritten identically by every chunk)
-    for (int c0 = 0; c0 < T; c0 += HEPT_MAX_TABLES) {
-        const int tc = T - c0 < HEPT_MAX_TABLES ? T - c0 : HEPT_MAX_TABLES;
-        // (K == 0: params->w_rpe is sqrt_w (H, C); K > 0: the weight itself, scale computed in the kernel -- see run_begin)
-        void* zptr = nullptr;
-        size_t zbytes = 0;
-        hept_sort_zero_block(w.sort_ws, N, H, tc, &zptr, &zbytes);   // (see run_begin)
-        rc = hept_prep_hash_fused_rpe(x, io_dtype, ldx, p->norm1_w, p->norm1_b, p->eps1, p->w_q, p->w_k, p->w_v, coords, p->w_rpe, K,
-                                      p->alpha, codes, N, raw_size, H, D, C, T, c0, tc, precision, w.qhat, w.kvhat, w.qproj,
-                                      w.kproj, w.minmax, stream, zptr, zbytes);
-        if (rc) return rc;
-        if (c0 == 0) prof_mark(1, st);
-        int32_t* cq = T <= HEPT_MAX_TABLES ? qpos : w.pos_chunk;
-        int32_t* ck = cq + (size_t)tc * H * N;
-        // (no rows job: the fused row builder writes the v half itself)
-        rc = geo.eta ? hept_sort_tables_src_rows(w.qproj, w.kproj, geo.eta, geo.phi, geo.cfac, w.minmax, N, H, T, c0, tc,
-                                                 w.sort_ws, cq, ck, nullptr, stream, zbytes != 0)
-                     : hept_sort_tables_rows(w.qproj, w.kproj, codes, w.minmax, N, H, T, c0, tc, w.sort_ws, cq, ck, nullptr,
-                                             stream, zbytes != 0);
-        if (rc) return rc;
-        if (cq != qpos) {
-            const size_t off = (size_t)c0 * H * N, bytes = (size_t)tc * H * N * 4;
-            if (hipMemcpyAsync(qpos + off, cq, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                hipMemcpyAsync(kpos + off, ck, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return HEPT_ERR_LAUNCH;
-        }
-    }
-    prof_mark(2, st);
-    rc = hept_block_attn(w.qhat, w.kvhat, qpos, kpos, N, H, D, T, B, precision, w.part, stream);
+    const int raw_size = geo.eta ? geo.raw_size : s.N;
+    // (K == 0: params->w_rpe is sqrt_w (H, C); K > 0: the weight itself, scale computed in the kernel -- see run_begin)
+    // (no rows job: the fused row builder writes the v half itself)
+    rc = walk_tables(s, codes, geo, w, nullptr, stream, [&](int t0, int tc, void* zptr, size_t zbytes) {
+        return hept_prep_hash_fused_rpe(x, io_dtype, ldx, p->norm1_w, p->norm1_b, p->eps1, p->w_q, p->w_k, p->w_v, coords,
+                                        p->w_rpe, s.K, p->alpha, codes, s.N, raw_size, s.H, s.D, s.C, s.T, t0, tc,
+                                        s.precision, w.qhat, w.kvhat, w.qproj, w.kproj, w.minmax, stream, zptr, zbytes);
+    });
+    if (rc) return rc;
+    rc = hept_block_attn(w.qhat, w.kvhat, w.pos, w.pos + (size_t)s.T * s.H * s.N, s.N, s.H, s.D, s.T, s.B, s.precision,
+                         w.part, stream);
     if (rc) return rc;
     prof_mark(3, st);
-    rc = hept_combine_ffn_ld(w.part, hept_part_precision(precision, D), T, N, H, D, 0, N, p->out_w, p->out_b, x, io_dtype,
-                             ldx, p->norm2_w, p->norm2_b, p->eps2, p->ff1_w, p->ff1_b, p->ff2_w, p->ff2_b, y, ldy, stream);
+    rc = hept_combine_ffn_ld(w.part, hept_part_precision(s.precision, s.D), s.T, s.N, s.H, s.D, 0, s.N, p->out_w, p->out_b,
+                             x, io_dtype, ldx, p->norm2_w, p->norm2_b, p->eps2, p->ff1_w, p->ff1_b, p->ff2_w, p->ff2_b, y,
+                             ldy, stream);
     prof_mark(4, st);
     prof_call_done();
     return rc;
@@ -750,24 +740,25 @@ int attn_block_impl(const void* x, int io_dtype, int ldx, const float* coords, c
 // in the workspace on every call (the sort's zero block, minmax, the rows), so the layers share it as consecutive
 // single-block calls on one module do.  Everything that can be refused is refused before the first HIP call.
 int attn_stack_impl(float* xcat, int ld, const float* coords, const int64_t* codes, const GeoShift& geo,
-                    const hept_attn_params* layers, int L, int N, int H, int D, int C, int K, int T, int B,
-                    int precision, void* workspace, size_t workspace_bytes, void* stream) {
+                    const hept_attn_params* layers, int L, const Sizes& s, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    const int N = s.N, H = s.H, D = s.D, C = s.C, K = s.K;
     if (!xcat || !coords || !layers || !workspace) return HEPT_ERR_ARG;
     for (int i = 0; i < L; ++i)
         if (attn_params_check(layers + i)) return HEPT_ERR_ARG;
     if (L < 1 || D != 24 || (long long)ld < ((long long)L + 1) * D || ld % 4 != 0) return HEPT_ERR_SHAPE;
-    int rc = hept_check_shape(N, H, D, C, T, B);
+    int rc = hept_check_shape(N, H, D, C, s.T, s.B);
     if (rc) return rc;
     if (geo.eta && (geo.raw_size < 0 || geo.raw_size > N)) return HEPT_ERR_SHAPE;
     if (K < 0 || (K > 0 && H * (C - 1) * K > 1024)) return HEPT_ERR_SHAPE;
     // D = 24: every column block starts at a multiple of 96 B, every row at a multiple of 4 ld B -- a 16-B aligned base
     // keeps all the f32x4 accesses of the row builder and of the combine's epilogue aligned
     if (reinterpret_cast<uintptr_t>(xcat) & 15) return HEPT_ERR_ARG;
-    if (workspace_bytes < carve(nullptr, N, H, C, T, precision).bytes) return HEPT_ERR_ARG;
+    if (workspace_bytes < carve(nullptr, N, H, C, s.T, s.precision).bytes) return HEPT_ERR_ARG;
     for (int i = 0; i < L; ++i) {
         // (each layer is one profiled call, like a single block: stage times per block stay comparable)
-        rc = attn_block_impl(xcat + (size_t)i * D, HEPT_IN_F32, ld, coords, codes, geo, layers + i, N, H, D, C, K, T, B, precision,
-                             workspace, workspace_bytes, xcat + (size_t)(i + 1) * D, ld, stream);
+        rc = attn_block_impl(xcat + (size_t)i * D, HEPT_IN_F32, ld, coords, codes, geo, layers + i, s, workspace,
+                             workspace_bytes, xcat + (size_t)(i + 1) * D, ld, stream);
         if (rc) return rc;
     }
     return HEPT_OK;
@@ -779,8 +770,8 @@ extern "C" int hept_attn_block_forward_io(const void* x, int io_dtype, const flo
                                           int precision, void* workspace, size_t workspace_bytes, void* y,
                                           void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return attn_block_impl(x, io_dtype, D, coords, codes, GeoShift{}, p, N, H, D, C, K, T, B, precision, workspace,
-                           workspace_bytes, y, D, stream);
+    return attn_block_impl(x, io_dtype, D, coords, codes, GeoShift{}, p, Sizes{N, H, D, C, K, T, 0, T, B, precision},
+                           workspace, workspace_bytes, y, D, stream);
 }
 
 extern "C" int hept_attn_block_forward(const float* x, const float* coords, const int64_t* codes,
@@ -796,10 +787,10 @@ extern "C" int hept_attn_block_forward_src_io(const void* x, int io_dtype, const
                                               const hept_attn_params* p, int N, int H, int D, int C, int K, int T,
                                               int B, int precision, void* workspace, size_t workspace_bytes, void* y,
                                               void* stream) {
-    if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
-    if (raw_size < 0 || raw_size > N) return HEPT_ERR_SHAPE;
-    return attn_block_impl(x, io_dtype, D, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, p, N, H, D, C, K,
-                           T, B, precision, workspace, workspace_bytes, y, D, stream);
+    GeoShift geo;
+    if (const int rc = geo_shift(eta_idx, phi_idx, cfac, raw_size, N, &geo)) return rc;
+    return attn_block_impl(x, io_dtype, D, coords, nullptr, geo, p, Sizes{N, H, D, C, K, T, 0, T, B, precision}, workspace,
+                           workspace_bytes, y, D, stream);
 }
 
 extern "C" int hept_attn_block_forward_src(const float* x, const float* coords, const float* eta_idx,
@@ -815,8 +806,8 @@ extern "C" int hept_attn_stack_forward(float* xcat, int ld, const float* coords,
                                        const hept_attn_params* layers, int L, int N, int H, int D, int C, int K, int T,
                                        int B, int precision, void* workspace, size_t workspace_bytes, void* stream) {
     if (!codes) return HEPT_ERR_ARG;
-    return attn_stack_impl(xcat, ld, coords, codes, GeoShift{}, layers, L, N, H, D, C, K, T, B, precision, workspace,
-                           workspace_bytes, stream);
+    return attn_stack_impl(xcat, ld, coords, codes, GeoShift{}, layers, L, Sizes{N, H, D, C, K, T, 0, T, B, precision},
+                           workspace, workspace_bytes, stream);
 }
 
 extern "C" int hept_attn_stack_forward_src(float* xcat, int ld, const float* coords, const float* eta_idx,
@@ -824,9 +815,10 @@ extern "C" int hept_attn_stack_forward_src(float* xcat, int ld, const float* coo
                                            const hept_attn_params* layers, int L, int N, int H, int D, int C, int K,
                                            int T, int B, int precision, void* workspace, size_t workspace_bytes,
                                            void* stream) {
+    // (the stack refuses a bad raw_size after its null pointers and its layer count: attn_stack_impl)
     if (!eta_idx || !phi_idx || !cfac) return HEPT_ERR_ARG;
-    return attn_stack_impl(xcat, ld, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, layers, L, N, H, D, C,
-                           K, T, B, precision, workspace, workspace_bytes, stream);
+    return attn_stack_impl(xcat, ld, coords, nullptr, GeoShift{eta_idx, phi_idx, cfac, raw_size}, layers, L,
+                           Sizes{N, H, D, C, K, T, 0, T, B, precision}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int hept_profile_enable(int mode, int max_calls) {

@@ -33,6 +33,12 @@ struct VSrc {
     int raw_size = 0;
 };
 
+// The q^ / k^|v rows of this precision hold f32 elements: "fp32" and the two modes that run other block-attention
+// kernels on the same rows.  The one spelling of that set: a new f32-row mode is added here and nowhere else.
+static inline bool hept_f32_rows(int precision) {
+    return precision == HEPT_PREC_F32 || precision == HEPT_PREC_F32_MFMA || precision == HEPT_PREC_F32_DIFF;
+}
+
 static inline int hept_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? HEPT_OK : HEPT_ERR_LAUNCH;

@@ -6,6 +6,7 @@ can check every stage against the oracle and inject permutations.
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 from typing import Dict, Optional, Tuple
 
@@ -133,6 +134,67 @@ def _check_shape_cached(n: int, h: int, d: int, c: int, tl: int, b: int) -> int:
     return int(_lib.load().hept_check_shape(n, h, d, c, tl, b))
 
 
+def _workspace(workspace, n, h, d, c, tl, b, prec, like, grow: bool = True) -> torch.Tensor:
+    """Shape check and workspace of a whole-operator call: ``workspace`` if it is large enough, else a new one on the
+    device of ``like`` -- or, for the callers whose workspace carries state from call to call (``grow=False``), a refusal."""
+    _lib.check(_check_shape_cached(n, h, d, c, tl, b), "hept_check_shape")
+    need = _workspace_bytes_cached(n, h, d, c, tl, b, prec)
+    if workspace is None or workspace.numel() < need:
+        if not grow:
+            raise ValueError(f"workspace too small: size it with ops.workspace_bytes ({need} bytes)")
+        workspace = torch.empty(need, device=like.device, dtype=torch.uint8)
+    return workspace
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
+
+
+def _out_linear(weight, bias):
+    """out_linear's weight and optional bias: their two pointers as the C ABI takes them, and the tensors they point into."""
+    w = _f32c(weight, "out_linear.weight")
+    if bias is None:
+        return (w.data_ptr(), None), w
+    b = _f32c(bias, "out_linear.bias")
+    return (w.data_ptr(), b.data_ptr()), (w, b)
+
+
+def _codes(codes: torch.Tensor, shape=None, exc=ValueError) -> torch.Tensor:
+    """The AND codes as the kernels read them: int64, on the GPU (a host address must never reach a kernel), contiguous,
+    (T, H, N) where the caller knows the sizes."""
+    if codes.dtype != torch.int64 or not codes.is_cuda or (shape is not None and codes.shape != shape):
+        raise exc(f"combined_shifts must be an int64 GPU tensor{'' if shape is None else f' of shape {shape}'}, "
+                  f"got {codes.dtype} {tuple(codes.shape)} on {codes.device}")
+    return codes.contiguous()
+
+
+def _raw_size(raw_size, n: int) -> int:
+    raw_size = int(raw_size)
+    if not 0 <= raw_size <= n:
+        raise ValueError(f"raw_size must lie in [0, {n}], got {raw_size}")
+    return raw_size
+
+
+# dtype tag of the row buffers: bf16 / f16 (mixed16: q^,k^ halves are fp16, the v half of kvhat is bf16) / f32
+_TILE = {PREC_F32: torch.float32, PREC_BF16: torch.bfloat16, PREC_MIXED16: torch.float16,
+         PREC_F32_MFMA: torch.float32, PREC_F32_DIFF: torch.float32}
+
+
+def _row_buffers(rows, prec: int, h: int, n: int, tl: int, dev) -> Dict[str, torch.Tensor]:
+    """Outputs of a row builder, in the order the C ABI takes them; ``rows`` = (qhat, kvhat) to reuse (``prep_hash``)."""
+    tile = _TILE[prec]
+    if rows is not None:
+        qhat, kvhat = rows
+        if qhat.dtype != tile or tuple(qhat.shape) != (h, n, 32) or kvhat.dtype != tile or tuple(kvhat.shape) != (h, n, 64):
+            raise ValueError("rows: buffers of another shape or precision")
+    else:
+        qhat = torch.empty(h, n, 32, device=dev, dtype=tile)
+        kvhat = torch.empty(h, n, 64, device=dev, dtype=tile)
+    return dict(qhat=qhat, kvhat=kvhat, qproj=torch.empty(tl, h, n, device=dev, dtype=torch.float32),
+                kproj=torch.empty(tl, h, n, device=dev, dtype=torch.float32),
+                minmax=torch.empty(tl, h, _lib.PREP_GRID, 4, device=dev, dtype=torch.float32))
+
+
 def workspace_bytes(n, h, d, c, tl, b, precision) -> int:
     return _workspace_bytes_cached(int(n), int(h), int(d), int(c), int(tl), int(b), precision_code(precision))
 
@@ -182,32 +244,15 @@ def prep_hash(q, k, v, coords, sqrt_w, alpha, codes, precision="fp32", t0: int =
     if tuple(sqrt_w.shape) != (h, c):   # the kernel indexes it as (H, C): a mismatch would be an out-of-bounds read
         raise ValueError(f"sqrt_w must have shape {(h, c)}, got {tuple(sqrt_w.shape)}")
     if codes is not None:
-        if codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n):
-            raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}")
-        codes = codes.contiguous()
+        codes = _codes(codes, (t, h, n))
     raw_size = n if raw_size is None else int(raw_size)
     tl = t - t0 if tl is None else tl
     prec = precision_code(precision)
-    # dtype tag of the row buffers: bf16 / f16 (mixed16: q^,k^ halves are fp16, the v half of kvhat is bf16) / f32
-    tile = {PREC_F32: torch.float32, PREC_BF16: torch.bfloat16, PREC_MIXED16: torch.float16,
-            PREC_F32_MFMA: torch.float32, PREC_F32_DIFF: torch.float32}[prec]
-    dev = q.device
-    if rows is not None:
-        qhat, kvhat = rows
-        if qhat.dtype != tile or tuple(qhat.shape) != (h, n, 32) or kvhat.dtype != tile or tuple(kvhat.shape) != (h, n, 64):
-            raise ValueError("rows: buffers of another shape or precision")
-    else:
-        qhat = torch.empty(h, n, 32, device=dev, dtype=tile)
-        kvhat = torch.empty(h, n, 64, device=dev, dtype=tile)
-    qproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
-    kproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
-    minmax = torch.empty(tl, h, _lib.PREP_GRID, 4, device=dev, dtype=torch.float32)
+    out = _row_buffers(rows, prec, h, n, tl, q.device)
     _lib.check(lib.hept_prep_hash_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), in_code, coords.data_ptr(),
-                                     sqrt_w.data_ptr(), alpha.data_ptr(), codes.data_ptr() if codes is not None else None,
-                                     n, raw_size, h, d, c, t, t0, tl, prec, qhat.data_ptr(), kvhat.data_ptr(),
-                                     qproj.data_ptr(), kproj.data_ptr(), minmax.data_ptr(), _stream(q)),
-               "hept_prep_hash")
-    return dict(qhat=qhat, kvhat=kvhat, qproj=qproj, kproj=kproj, minmax=minmax)
+                                     sqrt_w.data_ptr(), alpha.data_ptr(), _ptr(codes), n, raw_size, h, d, c, t, t0, tl, prec,
+                                     *(b.data_ptr() for b in out.values()), _stream(q)), "hept_prep_hash")
+    return out
 
 
 @_on_device
@@ -215,9 +260,7 @@ def sort_tables(qproj, kproj, codes, minmax, t0: int = 0) -> Tuple[torch.Tensor,
     """Stable ascending permutations (Tl,H,N) int32 of ``proj + float(code) * span`` for q and k."""
     lib = _lib.load()
     tl, h, n = qproj.shape
-    if codes.dtype != torch.int64 or not codes.is_cuda:
-        raise TypeError("combined_shifts must be an int64 GPU tensor")
-    codes = codes.contiguous()
+    codes = _codes(codes, exc=TypeError)
     t = codes.shape[0]
     ws = torch.empty(int(lib.hept_sort_workspace_bytes(n, h, tl)), device=qproj.device, dtype=torch.uint8)
     pos = torch.empty(2, tl, h, n, device=qproj.device, dtype=torch.int32)
@@ -327,12 +370,10 @@ def combine_out(part: torch.Tensor, head_dim: int, out_weight, out_bias, n0: int
         part = part.unsqueeze(0)
     tl, n, h, _ = part.shape
     n_count = n - n0 if n_count is None else n_count
-    w = _f32c(out_weight, "out_linear.weight")
-    b = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
+    out_linear, _keep = _out_linear(out_weight, out_bias)
     out = torch.empty(n_count, head_dim, device=part.device, dtype=torch.float32)
-    _lib.check(lib.hept_combine_out(part.data_ptr(), _part_prec(part), tl, n, h, head_dim, n0, n_count, w.data_ptr(),
-                                    b.data_ptr() if b is not None else None, out.data_ptr(), _stream(part)),
-               "hept_combine_out")
+    _lib.check(lib.hept_combine_out(part.data_ptr(), _part_prec(part), tl, n, h, head_dim, n0, n_count, *out_linear,
+                                    out.data_ptr(), _stream(part)), "hept_combine_out")
     return out
 
 
@@ -369,9 +410,8 @@ def block_attn_bwd(qhat, kvhat, qpos, kpos, gacc, head_dim: int, coords_dim: int
         coords = _f32c(coords, "coords")
         dsw = torch.empty(h, coords_dim, device=dev, dtype=torch.float32)
     _lib.check((lib.hept_bwd_reduce16 if rows16 else lib.hept_bwd_reduce)(dq_part.data_ptr(), dkv_part.data_ptr(), tl, n, h, head_dim, coords_dim,
-                                   coords.data_ptr() if coords is not None else None,
-                                   n if raw_size is None else int(raw_size), dq.data_ptr(), dk.data_ptr(),
-                                   dv.data_ptr(), dcs.data_ptr(), dsw.data_ptr() if dsw is not None else None, st),
+                                   _ptr(coords), n if raw_size is None else int(raw_size), dq.data_ptr(),
+                                   dk.data_ptr(), dv.data_ptr(), dcs.data_ptr(), _ptr(dsw), st),
                "hept_bwd_reduce")
     if coords is not None:
         return dq, dk, dv, dcs, dsw
@@ -392,8 +432,8 @@ def combine_bwd(acc: torch.Tensor, g_out: torch.Tensor, out_weight: torch.Tensor
     db = torch.empty(d, device=acc.device, dtype=torch.float32) if need_bias else None
     scratch = torch.empty(int(lib.hept_combine_bwd_scratch_bytes_shape(n, h, d)), device=acc.device, dtype=torch.uint8)
     _lib.check(lib.hept_combine_bwd(acc.data_ptr(), g_out.data_ptr(), w.data_ptr(), n, h, d, gacc.data_ptr(),
-                                    dw.data_ptr(), db.data_ptr() if db is not None else None, scratch.data_ptr(),
-                                    scratch.numel(), _stream(acc)), "hept_combine_bwd")
+                                    dw.data_ptr(), _ptr(db), scratch.data_ptr(), scratch.numel(), _stream(acc)),
+               "hept_combine_bwd")
     return gacc, dw, db
 
 
@@ -420,44 +460,70 @@ def _prepare(q, k, v, coords, codes, w_rpe_weight, alpha, block_size, w_per_dist
         q, k, v, _ = _qkv_in(q, k, v)
     else:
         q, k, v = (_f32c(x, nm) for x, nm in ((q, "query"), (k, "key"), (v, "value")))
-    coords, w, alpha = (_f32c(x, nm) for x, nm in
-                        ((coords, "coords"), (w_rpe_weight, "w_rpe.weight"), (alpha, "e2lsh.alpha")))
+    coords = _f32c(coords, "coords")
+    w = _f32c(w_rpe_weight, "w_rpe.weight")
+    alpha = _f32c(alpha, "e2lsh.alpha")
     n, h, d, c, t = _dims(q, coords, alpha)
     if k.shape != q.shape or v.shape != q.shape or coords.shape[0] != n:
         raise ValueError("query, key, value and coords must agree on the number of points")
     if n % block_size != 0:
         raise ValueError(f"number of points {n} is not a multiple of block_size {block_size}")
-    if codes is not None and (codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n)):
-        raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}, got {codes.dtype} {tuple(codes.shape)}")
+    if codes is not None:
+        codes = _codes(codes, (t, h, n))
     if w_per_dist == 0:  # precomputed sqrt_w (H, C) in place of the weight (hept_hip.h: K == 0)
         if w.shape != (h, c):
             raise ValueError(f"with w_per_dist=0 the weight argument is sqrt_w of shape {(h, c)}, got {tuple(w.shape)}")
     elif w.shape != (h * d, (c - 1) * w_per_dist):
         raise ValueError(f"w_rpe.weight must have shape {(h * d, (c - 1) * w_per_dist)}, got {tuple(w.shape)}")
-    return q, k, v, coords, codes.contiguous() if codes is not None else None, w, alpha, (n, h, d, c, t)
+    return q, k, v, coords, codes, w, alpha, (n, h, d, c, t)
+
+
+def _key_args(codes, geo, t: int, h: int, n: int, check: bool = False):
+    """The table-key arguments of an entry point (``geo`` is None: the AND codes) or of its ``*_src`` twin (``geo`` =
+    (region_indices, regions_h, raw_size)), as the C ABI takes them, and the tensors they point into.  ``check``: the
+    one-call blocks and stacks, where nothing has looked at ``codes`` yet and a bad ``raw_size`` is refused here."""
+    if geo is None:
+        codes = _codes(codes, (t, h, n)) if check else codes
+        return (codes.data_ptr(),), codes
+    region_indices, regions_h, raw_size = geo
+    keep = geo_args(region_indices, regions_h, t, h, n)
+    return (*(x.data_ptr() for x in keep), _raw_size(raw_size, n) if check else int(raw_size)), keep
+
+
+def _forward(q, k, v, coords, codes, geo, w_rpe_weight, alpha, out_weight, out_bias, block_size, w_per_dist, precision,
+             workspace, stream=None):
+    """``forward`` (``geo`` is None) and ``forward_src`` (``geo`` = (region_indices, regions_h, raw_size))."""
+    lib = _lib.load()
+    q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
+                                                                block_size, w_per_dist, in16=True)
+    keys, _keep = _key_args(codes, geo, t, h, n)
+    prec = precision_code(precision)
+    workspace = _workspace(workspace, n, h, d, c, t, block_size, prec, q)
+    out_linear, _keep_out = _out_linear(out_weight, out_bias)
+    out = torch.empty(n, d, device=q.device, dtype=torch.float32)
+    fn = lib.hept_forward_in if geo is None else lib.hept_forward_src_in
+    _lib.check(fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(), *keys, w.data_ptr(),
+                  alpha.data_ptr(), *out_linear, n, h, d, c, w_per_dist, t, block_size, prec,
+                  workspace.data_ptr(), workspace.numel(), out.data_ptr(), stream if stream is not None else _stream(q)),
+               fn.__name__)
+    return out
 
 
 @_on_device
 def forward(q, k, v, coords, codes, w_rpe_weight, alpha, out_weight, out_bias, *, block_size: int, w_per_dist: int,
             precision="fp32", workspace: Optional[torch.Tensor] = None, stream: Optional[int] = None) -> torch.Tensor:
     """Whole operator (reference ``example/hept.py:43-81``) in one C call; returns (N, D) float32."""
-    lib = _lib.load()
-    q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
-                                                                block_size, w_per_dist, in16=True)
-    prec = precision_code(precision)
-    _lib.check(_check_shape_cached(n, h, d, c, t, block_size), "hept_check_shape")
-    need = _workspace_bytes_cached(n, h, d, c, t, block_size, prec)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
-    ow = _f32c(out_weight, "out_linear.weight")
-    ob = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
-    out = torch.empty(n, d, device=q.device, dtype=torch.float32)
-    _lib.check(lib.hept_forward_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(),
-                                   codes.data_ptr(), w.data_ptr(), alpha.data_ptr(), ow.data_ptr(),
-                                   ob.data_ptr() if ob is not None else None, n, h, d, c, w_per_dist, t, block_size, prec,
-                                   workspace.data_ptr(), workspace.numel(), out.data_ptr(),
-                                   stream if stream is not None else _stream(q)), "hept_forward")
-    return out
+    return _forward(q, k, v, coords, codes, None, w_rpe_weight, alpha, out_weight, out_bias, block_size, w_per_dist,
+                    precision, workspace, stream)
+
+
+@_on_device
+def forward_src(q, k, v, coords, region_indices, regions_h, raw_size: int, w_rpe_weight, alpha, out_weight, out_bias,
+                *, block_size: int, w_per_dist: int, precision="fp32",
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Whole operator of the reference's src variant (``src/models/attention/hept.py:74-117``); (N, D) float32."""
+    return _forward(q, k, v, coords, None, (region_indices, regions_h, raw_size), w_rpe_weight, alpha, out_weight,
+                    out_bias, block_size, w_per_dist, precision, workspace)
 
 
 def packed_partials(precision, head_dim: int) -> bool:
@@ -465,8 +531,22 @@ def packed_partials(precision, head_dim: int) -> bool:
     return _lib.load().hept_part_precision(precision_code(precision), head_dim) == PREC_BF16
 
 
-def _acc_buffer(n, h, packed, device):
-    return torch.empty(n, h, 16 if packed else 32, device=device, dtype=torch.int32 if packed else torch.float32)
+def _forward_partial(q, k, v, coords, codes, geo, w_rpe_weight, alpha, block_size, w_per_dist, t0, tl, precision,
+                     workspace, packed):
+    """``forward_partial`` and ``forward_partial_src``; ``geo`` as in ``_forward``."""
+    lib = _lib.load()
+    q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
+                                                                block_size, w_per_dist, in16=True)
+    keys, _keep = _key_args(codes, geo, t, h, n)
+    prec = precision_code(precision)
+    workspace = _workspace(workspace, n, h, d, c, tl, block_size, prec, q)
+    acc = torch.empty(n, h, 16 if packed else 32, device=q.device, dtype=torch.int32 if packed else torch.float32)
+    fn = lib.hept_forward_partial_in if geo is None else lib.hept_forward_partial_src_in
+    _lib.check(fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(), *keys, w.data_ptr(),
+                  alpha.data_ptr(), n, h, d, c, w_per_dist, t, t0, tl, block_size, prec,
+                  PREC_BF16 if packed else PREC_F32, workspace.data_ptr(), workspace.numel(), acc.data_ptr(), _stream(q)),
+               fn.__name__)
+    return acc
 
 
 @_on_device
@@ -475,46 +555,8 @@ def forward_partial(q, k, v, coords, codes, w_rpe_weight, alpha, *, block_size: 
                     packed: bool = False) -> torch.Tensor:
     """Tables [t0, t0+tl) only: returns acc (N, H, 32) = sum over those tables of [numer | denom]; ``packed``:
     the same sum as packed rows (N, H, 16) int32 (needs ``packed_partials(precision, D)``)."""
-    lib = _lib.load()
-    q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
-                                                                block_size, w_per_dist, in16=True)
-    prec = precision_code(precision)
-    _lib.check(lib.hept_check_shape(n, h, d, c, tl, block_size), "hept_check_shape")
-    need = int(lib.hept_workspace_bytes(n, h, d, c, tl, block_size, prec))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
-    acc = _acc_buffer(n, h, packed, q.device)
-    _lib.check(lib.hept_forward_partial_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(),
-                                           codes.data_ptr(), w.data_ptr(), alpha.data_ptr(), n, h, d, c, w_per_dist, t,
-                                           t0, tl, block_size, prec, PREC_BF16 if packed else PREC_F32,
-                                           workspace.data_ptr(), workspace.numel(), acc.data_ptr(), _stream(q)),
-               "hept_forward_partial")
-    return acc
-
-
-@_on_device
-def forward_src(q, k, v, coords, region_indices, regions_h, raw_size: int, w_rpe_weight, alpha, out_weight, out_bias,
-                *, block_size: int, w_per_dist: int, precision="fp32",
-                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Whole operator of the reference's src variant (``src/models/attention/hept.py:74-117``); (N, D) float32."""
-    lib = _lib.load()
-    q, k, v, coords, _, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, None, w_rpe_weight, alpha, block_size,
-                                                             w_per_dist, in16=True)
-    eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
-    prec = precision_code(precision)
-    _lib.check(lib.hept_check_shape(n, h, d, c, t, block_size), "hept_check_shape")
-    need = int(lib.hept_workspace_bytes(n, h, d, c, t, block_size, prec))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
-    ow = _f32c(out_weight, "out_linear.weight")
-    ob = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
-    out = torch.empty(n, d, device=q.device, dtype=torch.float32)
-    _lib.check(lib.hept_forward_src_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype], coords.data_ptr(),
-                                       eta.data_ptr(), phi.data_ptr(), cfac.data_ptr(), int(raw_size), w.data_ptr(),
-                                       alpha.data_ptr(), ow.data_ptr(), ob.data_ptr() if ob is not None else None, n, h,
-                                       d, c, w_per_dist, t, block_size, prec, workspace.data_ptr(), workspace.numel(),
-                                       out.data_ptr(), _stream(q)), "hept_forward_src")
-    return out
+    return _forward_partial(q, k, v, coords, codes, None, w_rpe_weight, alpha, block_size, w_per_dist, t0, tl, precision,
+                            workspace, packed)
 
 
 @_on_device
@@ -522,23 +564,8 @@ def forward_partial_src(q, k, v, coords, region_indices, regions_h, raw_size: in
                         block_size: int, w_per_dist: int, t0: int, tl: int, precision="fp32",
                         workspace: Optional[torch.Tensor] = None, packed: bool = False) -> torch.Tensor:
     """src variant, tables [t0, t0+tl) only: acc (N, H, 32) = sum over those tables of [numer | denom]."""
-    lib = _lib.load()
-    q, k, v, coords, _, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, None, w_rpe_weight, alpha, block_size,
-                                                             w_per_dist, in16=True)
-    eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
-    prec = precision_code(precision)
-    _lib.check(lib.hept_check_shape(n, h, d, c, tl, block_size), "hept_check_shape")
-    need = int(lib.hept_workspace_bytes(n, h, d, c, tl, block_size, prec))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=q.device, dtype=torch.uint8)
-    acc = _acc_buffer(n, h, packed, q.device)
-    _lib.check(lib.hept_forward_partial_src_in(q.data_ptr(), k.data_ptr(), v.data_ptr(), _IN_CODE[q.dtype],
-                                               coords.data_ptr(), eta.data_ptr(), phi.data_ptr(), cfac.data_ptr(),
-                                               int(raw_size), w.data_ptr(), alpha.data_ptr(), n, h, d, c, w_per_dist, t,
-                                               t0, tl, block_size, prec, PREC_BF16 if packed else PREC_F32,
-                                               workspace.data_ptr(), workspace.numel(), acc.data_ptr(), _stream(q)),
-               "hept_forward_partial_src")
-    return acc
+    return _forward_partial(q, k, v, coords, None, (region_indices, regions_h, raw_size), w_rpe_weight, alpha, block_size,
+                            w_per_dist, t0, tl, precision, workspace, packed)
 
 
 @_on_device
@@ -563,32 +590,17 @@ def prep_hash_fused(x, norm_w, norm_b, eps, w_q, w_k, w_v, coords, sqrt_w, alpha
     if tuple(sqrt_w.shape) != (h, c):
         raise ValueError(f"sqrt_w must have shape {(h, c)}, got {tuple(sqrt_w.shape)}")
     if codes is not None:
-        if codes.dtype != torch.int64 or tuple(codes.shape) != (t, h, n):
-            raise ValueError(f"combined_shifts must be an int64 tensor of shape {(t, h, n)}")
-        codes = codes.contiguous()
+        codes = _codes(codes, (t, h, n))
     raw_size = n if raw_size is None else int(raw_size)
     tl = t - t0 if tl is None else tl
     prec = precision_code(precision)
-    dt = {PREC_F32: torch.float32, PREC_BF16: torch.bfloat16, PREC_MIXED16: torch.float16,
-            PREC_F32_MFMA: torch.float32, PREC_F32_DIFF: torch.float32}[prec]
-    dev = x.device
-    if rows is not None:   # see prep_hash
-        qhat, kvhat = rows
-        if qhat.dtype != dt or tuple(qhat.shape) != (h, n, 32) or kvhat.dtype != dt or tuple(kvhat.shape) != (h, n, 64):
-            raise ValueError("rows: buffers of another shape or precision")
-    else:
-        qhat = torch.empty(h, n, 32, device=dev, dtype=dt)
-        kvhat = torch.empty(h, n, 64, device=dev, dtype=dt)
-    qproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
-    kproj = torch.empty(tl, h, n, device=dev, dtype=torch.float32)
-    minmax = torch.empty(tl, h, _lib.PREP_GRID, 4, device=dev, dtype=torch.float32)
+    out = _row_buffers(rows, prec, h, n, tl, x.device)
     _lib.check(lib.hept_prep_hash_fused_in(x.data_ptr(), _IN_CODE[x.dtype], norm_w.data_ptr(), norm_b.data_ptr(),
                                            float(eps), w_q.data_ptr(), w_k.data_ptr(), w_v.data_ptr(), coords.data_ptr(),
-                                           sqrt_w.data_ptr(), alpha.data_ptr(),
-                                           codes.data_ptr() if codes is not None else None, n, raw_size, h, d, c, t, t0,
-                                           tl, prec, qhat.data_ptr(), kvhat.data_ptr(), qproj.data_ptr(),
-                                           kproj.data_ptr(), minmax.data_ptr(), _stream(x)), "hept_prep_hash_fused_in")
-    return {"qhat": qhat, "kvhat": kvhat, "qproj": qproj, "kproj": kproj, "minmax": minmax}
+                                           sqrt_w.data_ptr(), alpha.data_ptr(), _ptr(codes), n, raw_size, h, d, c, t, t0,
+                                           tl, prec, *(b.data_ptr() for b in out.values()), _stream(x)),
+               "hept_prep_hash_fused_in")
+    return out
 
 
 @_on_device
@@ -603,14 +615,13 @@ def combine_ffn(part: torch.Tensor, head_dim: int, out_weight, out_bias, x, norm
     tl, n, h, _ = part.shape
     n_count = n - n0 if n_count is None else n_count
     x = _inc(x, "x")
-    ts = [_f32c(t_, nm) for t_, nm in ((out_weight, "out_linear.weight"), (norm_w, "norm2.weight"),
-                                       (norm_b, "norm2.bias"), (ff1_w, "ff.0.weight"), (ff1_b, "ff.0.bias"),
-                                       (ff2_w, "ff.2.weight"), (ff2_b, "ff.2.bias"))]
-    ow, nw, nb, w1, b1, w2, b2 = ts
-    ob = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
+    out_linear, _keep = _out_linear(out_weight, out_bias)
+    nw, nb, w1, b1, w2, b2 = (_f32c(t_, nm) for t_, nm in ((norm_w, "norm2.weight"), (norm_b, "norm2.bias"),
+                                                           (ff1_w, "ff.0.weight"), (ff1_b, "ff.0.bias"),
+                                                           (ff2_w, "ff.2.weight"), (ff2_b, "ff.2.bias")))
     y = torch.empty(n_count, head_dim, device=part.device, dtype=x.dtype)
-    _lib.check(lib.hept_combine_ffn_io(part.data_ptr(), _part_prec(part), tl, n, h, head_dim, n0, n_count, ow.data_ptr(),
-                                       ob.data_ptr() if ob is not None else None, x[n0:].data_ptr(), _IN_CODE[x.dtype],
+    _lib.check(lib.hept_combine_ffn_io(part.data_ptr(), _part_prec(part), tl, n, h, head_dim, n0, n_count, *out_linear,
+                                       x[n0:].data_ptr(), _IN_CODE[x.dtype],
                                        nw.data_ptr(), nb.data_ptr(), float(eps), w1.data_ptr(), b1.data_ptr(),
                                        w2.data_ptr(), b2.data_ptr(), y.data_ptr(), _stream(part)), "hept_combine_ffn_io")
     return y
@@ -646,18 +657,28 @@ def _check_block(x_shape, coords, keep, num_heads, block_size, w_per_dist):
 def _block_args(x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace):
     """Checks and marshalling shared by the two one-call blocks: (x, coords, params struct, sizes, prec, workspace,
     the tensors the struct points into)."""
-    lib = _lib.load()
     x = _inc(x, "x")   # float32, bfloat16 or float16: the block reads the rows in place and answers in the same type
     coords = _f32c(coords, "coords")
     keep = {f: _f32c(params[k], k) for f, k in _BLOCK_NAMES.items()}
     n, h, d, c, t = _check_block(x.shape, coords, keep, num_heads, block_size, w_per_dist)
     prec = precision_code(precision)
-    _lib.check(lib.hept_check_shape(n, h, d, c, t, block_size), "hept_check_shape")
-    need = int(lib.hept_workspace_bytes(n, h, d, c, t, block_size, prec))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=x.device, dtype=torch.uint8)
+    workspace = _workspace(workspace, n, h, d, c, t, block_size, prec, x)
     st = _lib.AttnParams(**{f: v.data_ptr() for f, v in keep.items()}, eps1=float(eps1), eps2=float(eps2))
     return x, coords, st, (n, h, d, c, t), prec, workspace, keep
+
+
+def _attn_block_forward(x, coords, codes, geo, params, num_heads, block_size, w_per_dist, eps1, eps2, precision,
+                        workspace):
+    """``attn_block_forward`` and ``attn_block_forward_src``; ``geo`` as in ``_forward``."""
+    lib = _lib.load()
+    x, coords, st, (n, h, d, c, t), prec, workspace, _keep = _block_args(
+        x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace)
+    keys, _keep_keys = _key_args(codes, geo, t, h, n, check=True)
+    y = torch.empty(n, d, device=x.device, dtype=x.dtype)
+    fn = lib.hept_attn_block_forward_io if geo is None else lib.hept_attn_block_forward_src_io
+    _lib.check(fn(x.data_ptr(), _IN_CODE[x.dtype], coords.data_ptr(), *keys, ctypes.byref(st), n, h, d, c, w_per_dist, t,
+                  block_size, prec, workspace.data_ptr(), workspace.numel(), y.data_ptr(), _stream(x)), fn.__name__)
+    return y
 
 
 @_on_device
@@ -668,20 +689,8 @@ def attn_block_forward(x, coords, codes, params: Dict[str, torch.Tensor], *, num
     ``params`` holds the block's tensors under the reference's state-dict names.  ``x`` is float32, bfloat16 or float16
     and the result has its dtype: 16-bit rows are widened where the kernels load them and the float32 result is rounded
     once where it is stored -- bit for bit ``attn_block_forward(x.float(), ...).to(x.dtype)`` without the two casts."""
-    lib = _lib.load()
-    x, coords, st, (n, h, d, c, t), prec, workspace, _keep = _block_args(
-        x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace)
-    if codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n):
-        raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}")
-    codes = codes.contiguous()
-    y = torch.empty(n, d, device=x.device, dtype=x.dtype)
-    import ctypes
-
-    _lib.check(lib.hept_attn_block_forward_io(x.data_ptr(), _IN_CODE[x.dtype], coords.data_ptr(), codes.data_ptr(),
-                                              ctypes.byref(st), n, h, d, c, w_per_dist, t, block_size, prec,
-                                              workspace.data_ptr(), workspace.numel(), y.data_ptr(), _stream(x)),
-               "hept_attn_block_forward_io")
-    return y
+    return _attn_block_forward(x, coords, codes, None, params, num_heads, block_size, w_per_dist, eps1, eps2, precision,
+                               workspace)
 
 
 @_on_device
@@ -691,28 +700,13 @@ def attn_block_forward_src(x, coords, region_indices, regions_h, raw_size: int, 
     """The src variant's Attn block (reference ``src/models/baselines/transformer.py:205-214`` with
     ``attn_type="hept"``, eval mode) in one C call; the operator's kwargs as built by ``prepare_input_src``.  ``x`` and the
     result: float32, bfloat16 or float16, as for :func:`attn_block_forward`."""
-    lib = _lib.load()
-    x, coords, st, (n, h, d, c, t), prec, workspace, _keep = _block_args(
-        x, coords, params, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace)
-    eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
-    raw_size = int(raw_size)
-    if not 0 <= raw_size <= n:
-        raise ValueError(f"raw_size must lie in [0, {n}], got {raw_size}")
-    y = torch.empty(n, d, device=x.device, dtype=x.dtype)
-    import ctypes
-
-    _lib.check(lib.hept_attn_block_forward_src_io(x.data_ptr(), _IN_CODE[x.dtype], coords.data_ptr(), eta.data_ptr(),
-                                                  phi.data_ptr(), cfac.data_ptr(), raw_size, ctypes.byref(st), n, h, d,
-                                                  c, w_per_dist, t, block_size, prec, workspace.data_ptr(),
-                                                  workspace.numel(), y.data_ptr(), _stream(x)),
-               "hept_attn_block_forward_src_io")
-    return y
+    return _attn_block_forward(x, coords, None, (region_indices, regions_h, raw_size), params, num_heads, block_size,
+                               w_per_dist, eps1, eps2, precision, workspace)
 
 
 def _stack_args(xcat, coords, params_list, num_heads, block_size, w_per_dist, eps1, eps2, precision, workspace):
     """Checks and marshalling shared by the two one-call stacks: the checks of ``_block_args`` for every layer, an array
     of ``AttnParams``, and the pitch of the (N, ld) buffer (a column-sliced view is taken as it is)."""
-    lib = _lib.load()
     if xcat.dtype != torch.float32 or xcat.dim() != 2:
         raise TypeError(f"xcat must be a 2-d float32 tensor, got {xcat.dtype} with {xcat.dim()} dims")
     n_layers = len(params_list)
@@ -745,16 +739,28 @@ def _stack_args(xcat, coords, params_list, num_heads, block_size, w_per_dist, ep
         sts.append(_lib.AttnParams(**{f: v.data_ptr() for f, v in keep.items()}, eps1=float(eps1[i]), eps2=float(eps2[i])))
     n, h, d, c, t = dims0
     prec = precision_code(precision)
-    _lib.check(lib.hept_check_shape(n, h, d, c, t, block_size), "hept_check_shape")
-    need = int(lib.hept_workspace_bytes(n, h, d, c, t, block_size, prec))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=xcat.device, dtype=torch.uint8)
+    workspace = _workspace(workspace, n, h, d, c, t, block_size, prec, xcat)
     arr = (_lib.AttnParams * n_layers)(*sts)
     return coords, arr, n_layers, ld, dims0, prec, workspace, keeps
 
 
 def _eps_list(eps, n_layers: int):
     return [float(eps)] * n_layers if isinstance(eps, (int, float)) else [float(e) for e in eps]
+
+
+def _attn_stack_forward(xcat, coords, codes, geo, params_list, num_heads, block_size, w_per_dist, eps1, eps2, precision,
+                        workspace):
+    """``attn_stack_forward`` and ``attn_stack_forward_src``; ``geo`` as in ``_forward``."""
+    lib = _lib.load()
+    n_layers = len(params_list)
+    coords, arr, n_layers, ld, (n, h, d, c, t), prec, workspace, _keeps = _stack_args(
+        xcat, coords, params_list, num_heads, block_size, w_per_dist, _eps_list(eps1, n_layers),
+        _eps_list(eps2, n_layers), precision, workspace)
+    keys, _keep_keys = _key_args(codes, geo, t, h, n, check=True)
+    fn = lib.hept_attn_stack_forward if geo is None else lib.hept_attn_stack_forward_src
+    _lib.check(fn(xcat.data_ptr(), ld, coords.data_ptr(), *keys, arr, n_layers, n, h, d, c, w_per_dist, t, block_size,
+                  prec, workspace.data_ptr(), workspace.numel(), _stream(xcat)), fn.__name__)
+    return xcat
 
 
 @_on_device
@@ -765,18 +771,8 @@ def attn_stack_forward(xcat, coords, codes, params_list, *, num_heads: int, bloc
     buffer -- whose columns [0, D) hold the first layer's input; layer i writes columns [(i+1) D, (i+2) D) IN PLACE, so on
     return ``xcat`` is the reference's ``torch.cat(all_encoded_x, dim=-1)``.  ``eps1`` / ``eps2``: one value, or one per
     layer.  Returns ``xcat``."""
-    lib = _lib.load()
-    n_layers = len(params_list)
-    coords, arr, n_layers, ld, (n, h, d, c, t), prec, workspace, _keeps = _stack_args(
-        xcat, coords, params_list, num_heads, block_size, w_per_dist, _eps_list(eps1, n_layers),
-        _eps_list(eps2, n_layers), precision, workspace)
-    if codes.dtype != torch.int64 or not codes.is_cuda or tuple(codes.shape) != (t, h, n):
-        raise ValueError(f"combined_shifts must be an int64 GPU tensor of shape {(t, h, n)}")
-    codes = codes.contiguous()
-    _lib.check(lib.hept_attn_stack_forward(xcat.data_ptr(), ld, coords.data_ptr(), codes.data_ptr(), arr, n_layers, n, h,
-                                           d, c, w_per_dist, t, block_size, prec, workspace.data_ptr(),
-                                           workspace.numel(), _stream(xcat)), "hept_attn_stack_forward")
-    return xcat
+    return _attn_stack_forward(xcat, coords, codes, None, params_list, num_heads, block_size, w_per_dist, eps1, eps2,
+                               precision, workspace)
 
 
 @_on_device
@@ -785,20 +781,8 @@ def attn_stack_forward_src(xcat, coords, region_indices, regions_h, raw_size: in
                            workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``attn_stack_forward`` around the src variant's operator (the layer loop of
     ``src/models/baselines/transformer.py:133-144``); the operator's kwargs as built by ``prepare_input_src``."""
-    lib = _lib.load()
-    n_layers = len(params_list)
-    coords, arr, n_layers, ld, (n, h, d, c, t), prec, workspace, _keeps = _stack_args(
-        xcat, coords, params_list, num_heads, block_size, w_per_dist, _eps_list(eps1, n_layers),
-        _eps_list(eps2, n_layers), precision, workspace)
-    eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
-    raw_size = int(raw_size)
-    if not 0 <= raw_size <= n:
-        raise ValueError(f"raw_size must lie in [0, {n}], got {raw_size}")
-    _lib.check(lib.hept_attn_stack_forward_src(xcat.data_ptr(), ld, coords.data_ptr(), eta.data_ptr(), phi.data_ptr(),
-                                               cfac.data_ptr(), raw_size, arr, n_layers, n, h, d, c, w_per_dist, t,
-                                               block_size, prec, workspace.data_ptr(), workspace.numel(),
-                                               _stream(xcat)), "hept_attn_stack_forward_src")
-    return xcat
+    return _attn_stack_forward(xcat, coords, None, (region_indices, regions_h, raw_size), params_list, num_heads,
+                               block_size, w_per_dist, eps1, eps2, precision, workspace)
 
 
 @_on_device
@@ -811,20 +795,11 @@ def partial_begin(q, k, v, coords, codes, w_rpe_weight, alpha, *, block_size: in
     q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
                                                                 block_size, w_per_dist)
     prec = precision_code(precision)
-    _lib.check(lib.hept_check_shape(n, h, d, c, tl, block_size), "hept_check_shape")
-    if workspace.numel() < int(lib.hept_workspace_bytes(n, h, d, c, tl, block_size, prec)):
-        raise ValueError("workspace too small: size it with ops.workspace_bytes")
-    if geo is None:
-        rc = lib.hept_partial_begin(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), codes.data_ptr(),
-                                    w.data_ptr(), alpha.data_ptr(), n, h, d, c, w_per_dist, t, t0, tl, block_size, prec,
-                                    workspace.data_ptr(), workspace.numel(), _stream(q))
-    else:
-        region_indices, regions_h, raw_size = geo
-        eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
-        rc = lib.hept_partial_begin_src(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), eta.data_ptr(),
-                                        phi.data_ptr(), cfac.data_ptr(), int(raw_size), w.data_ptr(), alpha.data_ptr(),
-                                        n, h, d, c, w_per_dist, t, t0, tl, block_size, prec, workspace.data_ptr(),
-                                        workspace.numel(), _stream(q))
+    _workspace(workspace, n, h, d, c, tl, block_size, prec, q, grow=False)
+    keys, _keep = _key_args(codes, geo, t, h, n)
+    fn = lib.hept_partial_begin if geo is None else lib.hept_partial_begin_src
+    rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), *keys, w.data_ptr(), alpha.data_ptr(), n, h, d,
+            c, w_per_dist, t, t0, tl, block_size, prec, workspace.data_ptr(), workspace.numel(), _stream(q))
     _lib.check(rc, "hept_partial_begin")
     return n, h, d, c
 
@@ -856,12 +831,11 @@ def combine_groups(part: torch.Tensor, head_dim: int, out_weight, out_bias, n0: 
         raise ValueError("part must be a contiguous (groups, tables, points, heads per group, row) tensor")
     g, tl, n, hg, row = part.shape
     n_count = n - n0 if n_count is None else n_count
-    w = _f32c(out_weight, "out_linear.weight")
-    b = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
+    out_linear, _keep = _out_linear(out_weight, out_bias)
     out = torch.empty(n_count, head_dim, device=part.device, dtype=torch.float32)
     _lib.check(lib.hept_combine_groups(part.data_ptr(), _part_prec(part), tl, n, g * hg, head_dim, n0, n_count, hg,
-                                       tl * n * hg * row, w.data_ptr(), b.data_ptr() if b is not None else None,
-                                       out.data_ptr(), _stream(part)), "hept_combine_groups")
+                                       tl * n * hg * row, *out_linear, out.data_ptr(), _stream(part)),
+               "hept_combine_groups")
     return out
 
 
@@ -881,35 +855,21 @@ def forward_sharded(q, k, v, coords, codes, w_rpe_weight, alpha, out_weight, out
     q, k, v, coords, codes, w, alpha, (n, h, d, c, t) = _prepare(q, k, v, coords, codes, w_rpe_weight, alpha,
                                                                 block_size, w_per_dist)
     prec = precision_code(precision)
-    _lib.check(lib.hept_check_shape(n, h, d, c, tl, block_size), "hept_check_shape")
-    if workspace.numel() < int(lib.hept_workspace_bytes(n, h, d, c, tl, block_size, prec)):
-        raise ValueError("workspace too small: size it with ops.workspace_bytes")
+    _workspace(workspace, n, h, d, c, tl, block_size, prec, q, grow=False)
     if not one_sided and (xbuf is None or xbuf.numel() < int(lib.hept_exchange_bytes(n, h, d, world, prec))):
         raise ValueError("exchange buffer too small: size it with hept_exchange_bytes")
-    ow = _f32c(out_weight, "out_linear.weight")
-    ob = _f32c(out_bias, "out_linear.bias") if out_bias is not None else None
+    out_linear, _keep_out = _out_linear(out_weight, out_bias)
     per = (n + world - 1) // world
     view = bool(out_view and one_sided)
     out_full = None if view else torch.empty(per * world, d, device=q.device, dtype=torch.float32)
-    tail = (n, h, d, c, w_per_dist, t, t0, tl, block_size, prec, head_groups,
+    keys, _keep = _key_args(codes, geo, t, h, n)
+    fn = lib.hept_forward_sharded if geo is None else lib.hept_forward_sharded_src
+    rc = fn(comm, q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(), *keys, w.data_ptr(), alpha.data_ptr(),
+            *out_linear, n, h, d, c, w_per_dist, t, t0, tl, block_size, prec, head_groups,
             _lib.TRANSPORT_ONE_SIDED if one_sided else _lib.TRANSPORT_RCCL, workspace.data_ptr(), workspace.numel(),
-            xbuf.data_ptr() if xbuf is not None else None, xbuf.numel() if xbuf is not None else 0,
-            out_full.data_ptr() if out_full is not None else None, _stream(q))
-    if geo is None:
-        rc = lib.hept_forward_sharded(comm, q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(),
-                                      codes.data_ptr(), w.data_ptr(), alpha.data_ptr(), ow.data_ptr(),
-                                      ob.data_ptr() if ob is not None else None, *tail)
-    else:
-        region_indices, regions_h, raw_size = geo
-        eta, phi, cfac = geo_args(region_indices, regions_h, t, h, n)
-        rc = lib.hept_forward_sharded_src(comm, q.data_ptr(), k.data_ptr(), v.data_ptr(), coords.data_ptr(),
-                                          eta.data_ptr(), phi.data_ptr(), cfac.data_ptr(), int(raw_size), w.data_ptr(),
-                                          alpha.data_ptr(), ow.data_ptr(), ob.data_ptr() if ob is not None else None,
-                                          *tail)
+            _ptr(xbuf), xbuf.numel() if xbuf is not None else 0, _ptr(out_full), _stream(q))
     _lib.check(rc, "hept_forward_sharded")
     if view:
-        import ctypes
-
         ptr = ctypes.c_void_p()
         _lib.check(lib.hept_comm_out_view(comm, ctypes.byref(ptr)), "hept_comm_out_view")
         return torch.as_tensor(_DeviceRows(ptr.value, n, d, view_owner), device=q.device)
@@ -948,8 +908,7 @@ def rows_wgrad(d_y: torch.Tensor, x: torch.Tensor, need_bias: bool = False):
     db = torch.empty(o, device=x.device, dtype=torch.float32) if need_bias else None
     scratch = torch.empty(int(lib.hept_rows_wgrad_scratch_bytes(n, o)), device=x.device, dtype=torch.uint8)
     _lib.check(lib.hept_rows_wgrad(d_y.data_ptr(), x.data_ptr(), n, o, 24, dw.data_ptr(),
-                                   db.data_ptr() if db is not None else None, scratch.data_ptr(), scratch.numel(),
-                                   _stream(x)), "hept_rows_wgrad")
+                                   _ptr(db), scratch.data_ptr(), scratch.numel(), _stream(x)), "hept_rows_wgrad")
     return (dw, db) if need_bias else dw
 
 
@@ -1015,8 +974,6 @@ def profile_stride(stride: int) -> None:
 
 def profile_read() -> Tuple[Dict[str, float], int]:
     """Summed milliseconds per stage over the recorded calls, and the number of calls; resets the pool."""
-    import ctypes
-
     ms = (ctypes.c_float * 7)()
     n = ctypes.c_int(0)
     _lib.check(_lib.load().hept_profile_read(ms, ctypes.byref(n)), "hept_profile_read")

@@ -111,3 +111,16 @@ def test_pad_and_unpad_small_cloud_window():
     by_code = torch.sort(codes, stable=True).indices
     assert pad_seq[5:8].tolist() == by_code[1:4].tolist()      # sorted positions [5-4, 5-4+3)
     assert pad_seq[11].item() == by_code[4].item()             # sorted position 8-4
+
+
+def test_ops_refuses_codes_a_kernel_could_not_read():
+    """The one combined_shifts check of ``hept_amd.ops``, shared by every caller that hands the codes to a kernel: a
+    host tensor (its address must never reach a kernel), another dtype, another shape."""
+    from hept_amd import ops
+
+    t, h, n = 3, 8, 256
+    for codes in (torch.zeros(t, h, n, dtype=torch.int64),      # right dtype and shape, but in host memory
+                  torch.zeros(t, h, n, dtype=torch.int32),
+                  torch.zeros(t, h, n - 1, dtype=torch.int64)):
+        with pytest.raises(ValueError, match="combined_shifts must be an int64 GPU tensor of shape"):
+            ops._codes(codes, (t, h, n))
