@@ -76,6 +76,7 @@ SIGNATURES = {
     "hept_forward_partial_src_in": (c_int, [_P] * 3 + [c_int] + [_P] * 4 + [c_int] + [_P] * 2 + [c_int] * 11 + [_P, c_size_t, _P, _P]),
     "hept_block_attn_bwd": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),
     "hept_block_attn_bwd_f32mfma": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),
+    "hept_block_attn_bwd_diff": (c_int, [_P] * 5 + [c_int] * 6 + [_P] * 3),
     "hept_block_attn_bwd_bf16": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),
     "hept_bwd_reduce": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_int] + [_P] * 6),
     "hept_bwd_reduce16": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_int] + [_P] * 6),

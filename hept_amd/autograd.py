@@ -88,6 +88,10 @@ class HeptPartialSums(torch.autograd.Function):
     ``tiles``: "fp32" (the reference's arithmetic; split-bf16 products in both directions) or "bf16" (the rows and
     kernels of the bf16 forward, one bf16 MFMA per product in the backward too -- ``HEPTAttention.train_tiles``).
 
+    ``f32_mfma``: handed unchanged to ``ops.block_attn`` and ``ops.block_attn_bwd`` -- False (split-bf16 products), True
+    (native f32 MFMA) or "diff" (``precision="fp32_diff"``: the difference form in both directions, so that the node's
+    forward is the kernel the inference path runs).
+
     ``geo`` = (eta, phi, cfac, raw_size) selects the reference's src variant (``codes`` is then None): rows at and
     after ``raw_size`` are zero-filled in place by the reference (``src/models/attention/hept.py:89-91``), so no
     gradient flows into them.

@@ -35,11 +35,26 @@ __device__ __forceinline__ void lds_half_row(const char* tile, int row, int hh, 
     }
 }
 
-template <int NKT, bool FULL>
+// DIFF (hept_block_attn_bwd_diff, precision "fp32_diff"): the backward of block_attn_kernel<.., DIFF>.  With a trained
+// w_rpe on raw coordinates the expanded logit is rounding noise (block_attn.hip), and so is a P recomputed from it.
+//   logits, both phases: the feature columns d < D through the MFMA against feature-only norms formed here, every
+//     coordinate column c in [D, D + C) as -(q^_c - k^_c)^2 / 2 from the two staged values -- the forward's arithmetic
+//     in the forward's order, so the recomputed P is the forward's P;
+//   coordinate columns of d q^ / d k^: sum_j dS_ij (k^_c[j] - q^_c[i]) summed as written, on the VALU.  (Z - rowsum(dS) q^
+//     subtracts two numbers of order 1e4 x the result there; the feature columns, O(10), keep it.)  In the
+//     accumulator layout a lane owns a query (a key) and its registers run over the other side: 16 fmaf per column and
+//     tile, the two lane halves meet in one __shfl_xor at the end, and the owning lane stores the value where the MFMA
+//     result of that column is not stored.
+// One launch accumulates at most BWD_DIFF_COLS coordinate columns, [D + c0, D + c0 + BWD_DIFF_COLS) -- compile-time
+// register indices; every shape of the reference has C <= 6, wider rows take ceil(C / 6) launches, each of which
+// rewrites the same feature columns.
+constexpr int BWD_DIFF_COLS = 6;
+
+template <int NKT, bool FULL, bool DIFF = false>
 __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
     const float* __restrict__ qhat, const float* __restrict__ kvhat, const int* __restrict__ qpos,
     const int* __restrict__ kpos, const float* __restrict__ gacc, float* __restrict__ dq_part,
-    float* __restrict__ dkv_part, int N, int H, int D, int B, int nb) {
+    float* __restrict__ dkv_part, int N, int H, int D, int B, int nb, int C, int c0) {
     constexpr int NT = 64 * NKT, ROWS = 32 * NKT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* q_s = smem;                      // [ROWS][32 f32] swizzled, column 30 = 1.0, column 31 = 0
@@ -50,6 +65,10 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
     float* kn_s = qn_s + ROWS;
     int* qidx_s = reinterpret_cast<int*>(kn_s + ROWS);
     int* kidx_s = qidx_s + ROWS;
+    // DIFF: the launch's coordinate columns of q^ and k^ again, [ROWS][8] unswizzled (zero past the last one): a row of
+    // the accumulator layout is then the lane's base plus a compile-time offset
+    float* cq_s = reinterpret_cast<float*>(kidx_s + ROWS);
+    float* ck_s = cq_s + ROWS * 8;
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hh = lane >> 5, li = lane & 31;
     const int bid = blockIdx.x;
@@ -103,6 +122,26 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
             *reinterpret_cast<f32x4*>(v_s + sw_byte(row, c - 8)) = x;
     }
     __syncthreads();
+    constexpr int CW = DIFF ? BWD_DIFF_COLS : 1;
+    const int cn = DIFF ? min(BWD_DIFF_COLS, C - c0) : 0;   // coordinate columns D + c0 .. D + c0 + cn - 1 of this launch
+    if constexpr (DIFF) {
+        // -|q|^2 / 2 and -|k|^2 / 2 over the feature columns (the stored norms cover the coordinate columns too), summed
+        // as the forward sums them: a key's columns in order, a query's in two halves of 16 columns
+        const bool isq = tid < ROWS;   // NT = 2 ROWS: one thread per staged row
+        const int row = isq ? tid : tid - ROWS;
+        const char* tile = isq ? q_s : k_s;
+        float lo = 0.f, hi = 0.f;
+        for (int col = 0; col < D; ++col) {
+            const float x = lds_elem(tile, row, col);
+            if (isq && col >= 16) hi = fmaf(x, x, hi);
+            else lo = fmaf(x, x, lo);
+        }
+        (isq ? qn_s : kn_s)[row] = -0.5f * (lo + hi);
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            (isq ? cq_s : ck_s)[row * 8 + c] = c < cn ? lds_elem(tile, row, D + c0 + c) : 0.f;
+        __syncthreads();
+    }
 
     const int own = w * 32 + li;  // the query (phase Q) / key (phase K) of this lane
     const bool own_ok = FULL || own < B;
@@ -113,13 +152,26 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
         lds_half_row(q_s, own, hh, qreg);
         lds_half_row(g_s, own, hh, greg);
         if (hh == 1) qreg[14] = 0.f;  // the 1.0 of column 30 is not a feature
+        float qc[CW], dc[CW];   // DIFF: this query's coordinate columns and their gradient
+        if constexpr (DIFF) {
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if (16 * hh + s >= D) qreg[s] = 0.f;   // everything from column D on leaves the matrix product
+#pragma unroll
+            for (int c = 0; c < CW; ++c) {
+                qc[c] = cq_s[own * 8 + c];
+                dc[c] = 0.f;
+            }
+        }
         const float qn = qn_s[own];
         f32x16 z;
 #pragma unroll
         for (int r = 0; r < 16; ++r) z[r] = 0.f;
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
-            if (!FULL && kt * 32 >= B) break;
+            // (DIFF keeps the never-taken exit on full blocks too: without it the scheduler hoists the reads of
+            //  every tile to the top and the kernel spills)
+            if ((!FULL || DIFF) && kt * 32 >= B) break;
             f32x16 x, y;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -133,12 +185,34 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
             for (int s = 0; s < 16; ++s) x = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qreg[s], x, 0, 0, 0);
 #pragma unroll
             for (int s = 0; s < 16; ++s) y = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[s], greg[s], y, 0, 0, 0);
+            if constexpr (DIFF) {
+                float dsq[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dsq[r] = 0.f;
+                for (int col = D; col < D + C; ++col) {
+                    const float qv = lds_elem(q_s, own, col);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float dlt = qv - lds_elem(k_s, kt * 32 + hept_acc_row(r, hh), col);
+                        dsq[r] = fmaf(dlt, dlt, dsq[r]);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) x[r] = fmaf(-0.5f, dsq[r], x[r]);
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kt * 32 + hept_acc_row(r, hh);
                 float ds = x[r] <= 0.f ? fminf(__expf(x[r]), 1.f) * y[r] : 0.f;
                 if (!FULL && (key >= B || !own_ok)) ds = 0.f;
                 z = __builtin_amdgcn_mfma_f32_32x32x2f32(ds, lds_elem(k_s, key, li), z, 0, 0, 0);
+                if constexpr (DIFF) {   // (columns past the launch's last one are zero on both sides)
+                    const f32x4 k03 = *reinterpret_cast<const f32x4*>(ck_s + key * 8);
+                    const hept_f32x2 k45 = *reinterpret_cast<const hept_f32x2*>(ck_s + key * 8 + 4);
+                    const float kcr[BWD_DIFF_COLS] = {k03[0], k03[1], k03[2], k03[3], k45[0], k45[1]};
+#pragma unroll
+                    for (int c = 0; c < CW; ++c) dc[c] = fmaf(ds, kcr[c] - qc[c], dc[c]);
+                }
             }
         }
         // d q^_i = sum_j dS_ij k^_j - (sum_j dS_ij) q^_i ;  lane = column, registers = queries
@@ -147,7 +221,16 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
         for (int r = 0; r < 16; ++r) {
             const int q2 = w * 32 + hept_acc_row(r, hh);
             const float rs = __shfl(z[r], 30 + 32 * hh);
-            if (FULL || q2 < B) dst[(size_t)qidx_s[q2] * H * 32] = z[r] - rs * lds_elem(q_s, q2, li);
+            if ((FULL || q2 < B) && !(DIFF && li >= D && li < D + C))
+                dst[(size_t)qidx_s[q2] * H * 32] = z[r] - rs * lds_elem(q_s, q2, li);
+        }
+        if constexpr (DIFF) {   // the coordinate columns: the two halves of the lane pair hold the two halves of the keys
+#pragma unroll
+            for (int c = 0; c < CW; ++c) {
+                if (c >= cn) break;
+                const float tot = dc[c] + __shfl_xor(dc[c], 32);
+                if (hh == 0 && own_ok) (dst - li)[(size_t)qidx_s[own] * H * 32 + D + c0 + c] = tot;
+            }
         }
     }
 
@@ -157,13 +240,26 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
         lds_half_row(k_s, own, hh, kreg);
         lds_half_row(v_s, own, hh, vreg);
         if (hh == 1) kreg[14] = 0.f;
+        float kc[CW], dc[CW];   // DIFF: this key's coordinate columns and their gradient
+        if constexpr (DIFF) {
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if (16 * hh + s >= D) kreg[s] = 0.f;
+#pragma unroll
+            for (int c = 0; c < CW; ++c) {
+                kc[c] = ck_s[own * 8 + c];
+                dc[c] = 0.f;
+            }
+        }
         const float kn = kn_s[own];
         f32x16 zk, zv;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { zk[r] = 0.f; zv[r] = 0.f; }
 #pragma unroll
         for (int qt = 0; qt < NKT; ++qt) {
-            if (!FULL && qt * 32 >= B) break;
+            // (DIFF keeps the never-taken exit on full blocks too: without it the scheduler hoists the reads of
+            //  every tile to the top and the kernel spills)
+            if ((!FULL || DIFF) && qt * 32 >= B) break;
             f32x16 x, y;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -177,6 +273,21 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
             for (int s = 0; s < 16; ++s) x = __builtin_amdgcn_mfma_f32_32x32x2f32(qf[s], kreg[s], x, 0, 0, 0);
 #pragma unroll
             for (int s = 0; s < 16; ++s) y = __builtin_amdgcn_mfma_f32_32x32x2f32(gf[s], vreg[s], y, 0, 0, 0);
+            if constexpr (DIFF) {
+                float dsq[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) dsq[r] = 0.f;
+                for (int col = D; col < D + C; ++col) {
+                    const float kv = lds_elem(k_s, own, col);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float dlt = lds_elem(q_s, qt * 32 + hept_acc_row(r, hh), col) - kv;
+                        dsq[r] = fmaf(dlt, dlt, dsq[r]);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) x[r] = fmaf(-0.5f, dsq[r], x[r]);
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int qry = qt * 32 + hept_acc_row(r, hh);
@@ -185,6 +296,13 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
                 const float ds = x[r] <= 0.f ? p * y[r] : 0.f;
                 zk = __builtin_amdgcn_mfma_f32_32x32x2f32(ds, lds_elem(q_s, qry, li), zk, 0, 0, 0);
                 zv = __builtin_amdgcn_mfma_f32_32x32x2f32(p, lds_elem(g_s, qry, li), zv, 0, 0, 0);
+                if constexpr (DIFF) {
+                    const f32x4 q03 = *reinterpret_cast<const f32x4*>(cq_s + qry * 8);
+                    const hept_f32x2 q45 = *reinterpret_cast<const hept_f32x2*>(cq_s + qry * 8 + 4);
+                    const float qcr[BWD_DIFF_COLS] = {q03[0], q03[1], q03[2], q03[3], q45[0], q45[1]};
+#pragma unroll
+                    for (int c = 0; c < CW; ++c) dc[c] = fmaf(ds, qcr[c] - kc[c], dc[c]);
+                }
             }
         }
         float* __restrict__ dst = dkv_part + (size_t)t * N * H * 64 + (size_t)h * 64 + li;
@@ -194,8 +312,16 @@ __global__ __launch_bounds__(64 * NKT) void block_attn_bwd_kernel(
             const float rs = __shfl(zk[r], 30 + 32 * hh);
             if (FULL || k2 < B) {
                 float* row = dst + (size_t)kidx_s[k2] * H * 64;
-                row[0] = zk[r] - rs * lds_elem(k_s, k2, li);
+                if (!(DIFF && li >= D && li < D + C)) row[0] = zk[r] - rs * lds_elem(k_s, k2, li);
                 row[32] = li < D ? zv[r] : 0.f;
+            }
+        }
+        if constexpr (DIFF) {
+#pragma unroll
+            for (int c = 0; c < CW; ++c) {
+                if (c >= cn) break;
+                const float tot = dc[c] + __shfl_xor(dc[c], 32);
+                if (hh == 0 && own_ok) (dst - li)[(size_t)kidx_s[own] * H * 64 + D + c0 + c] = tot;
             }
         }
     }
@@ -811,19 +937,20 @@ __global__ __launch_bounds__(256) void dsw_sum_kernel(const float* __restrict__ 
     if (threadIdx.x < HEPT_FSUM_OUT && o < HC) d_sqrt_w[o] = tot;
 }
 
-template <bool FULL>
+template <bool FULL, bool DIFF = false>
 int launch_bwd(int nkt, dim3 grid, hipStream_t st, const float* qhat, const float* kvhat, const int* qpos,
                const int* kpos, const float* gacc, float* dq_part, float* dkv_part, int N, int H, int D, int B,
-               int nb) {
+               int nb, int C = 0) {
 #define HEPT_BWD_CASE(K)                                                                                         \
     case K: {                                                                                                    \
-        constexpr size_t lds = (size_t)4 * 32 * K * 128 + 32 * K * 16;                                           \
+        constexpr size_t lds = (size_t)4 * 32 * K * 128 + 32 * K * 16 + (DIFF ? 32 * K * 64 : 0);                \
         static LdsRaised raised;                                                                                 \
         if (lds > 65536 &&                                                                                       \
-            hept_raise_lds(raised, reinterpret_cast<const void*>(&block_attn_bwd_kernel<K, FULL>), lds))         \
+            hept_raise_lds(raised, reinterpret_cast<const void*>(&block_attn_bwd_kernel<K, FULL, DIFF>), lds))   \
             return HEPT_ERR_LAUNCH;                                                                              \
-        hipLaunchKernelGGL((block_attn_bwd_kernel<K, FULL>), grid, dim3(64 * K), lds, st, qhat, kvhat, qpos,     \
-                           kpos, gacc, dq_part, dkv_part, N, H, D, B, nb);                                       \
+        for (int c0 = 0; c0 < (DIFF ? C : 1); c0 += BWD_DIFF_COLS) /* DIFF: six coordinate columns per launch */ \
+            hipLaunchKernelGGL((block_attn_bwd_kernel<K, FULL, DIFF>), grid, dim3(64 * K), lds, st, qhat, kvhat, \
+                               qpos, kpos, gacc, dq_part, dkv_part, N, H, D, B, nb, C, c0);                      \
         break;                                                                                                   \
     }
     switch (nkt) {
@@ -904,17 +1031,24 @@ int launch_bwd_bf16(int nkt, dim3 grid, hipStream_t st, const char* qhat, const 
     return hept_launch_status();
 }
 
-int block_attn_bwd_impl(bool split, const float* qhat, const float* kvhat, const int32_t* qpos, const int32_t* kpos,
-                        const float* gacc, int N, int H, int D, int Tl, int B, float* dq_part, float* dkv_part,
+enum BwdKernel { BWD_SPLIT, BWD_F32MFMA, BWD_DIFF };
+
+// C: the coordinate columns [D, D + C) of the rows (BWD_DIFF only; the other kernels treat every column alike)
+int block_attn_bwd_impl(BwdKernel kernel, const float* qhat, const float* kvhat, const int32_t* qpos, const int32_t* kpos,
+                        const float* gacc, int N, int H, int D, int C, int Tl, int B, float* dq_part, float* dkv_part,
                         void* stream) {
     if (!qhat || !kvhat || !qpos || !kpos || !gacc || !dq_part || !dkv_part) return HEPT_ERR_ARG;
     if (N < 1 || H < 1 || Tl < 1 || B < 1 || B > HEPT_MAX_BLOCK || N % B != 0 || D < 1 || D > 28)
         return HEPT_ERR_SHAPE;
+    if (kernel == BWD_DIFF && (C < 1 || D + C > 30)) return HEPT_ERR_SHAPE;
     const int nb = N / B, nkt = (B + 31) / 32;
     const dim3 grid((unsigned)((size_t)Tl * nb * H));
     hipStream_t st = (hipStream_t)stream;
     const bool full = B == 32 * nkt;
-    if (split)
+    if (kernel == BWD_DIFF)
+        return full ? launch_bwd<true, true>(nkt, grid, st, qhat, kvhat, qpos, kpos, gacc, dq_part, dkv_part, N, H, D, B, nb, C)
+                    : launch_bwd<false, true>(nkt, grid, st, qhat, kvhat, qpos, kpos, gacc, dq_part, dkv_part, N, H, D, B, nb, C);
+    if (kernel == BWD_SPLIT)
         return full ? launch_bwd_split<true>(nkt, grid, st, qhat, kvhat, qpos, kpos, gacc, dq_part, dkv_part, N, H, D, B, nb)
                     : launch_bwd_split<false>(nkt, grid, st, qhat, kvhat, qpos, kpos, gacc, dq_part, dkv_part, N, H, D, B, nb);
     return full ? launch_bwd<true>(nkt, grid, st, qhat, kvhat, qpos, kpos, gacc, dq_part, dkv_part, N, H, D, B, nb)
@@ -926,13 +1060,19 @@ int block_attn_bwd_impl(bool split, const float* qhat, const float* kvhat, const
 extern "C" int hept_block_attn_bwd(const float* qhat, const float* kvhat, const int32_t* qpos, const int32_t* kpos,
                                    const float* gacc, int N, int H, int D, int Tl, int B, float* dq_part,
                                    float* dkv_part, void* stream) {
-    return block_attn_bwd_impl(true, qhat, kvhat, qpos, kpos, gacc, N, H, D, Tl, B, dq_part, dkv_part, stream);
+    return block_attn_bwd_impl(BWD_SPLIT, qhat, kvhat, qpos, kpos, gacc, N, H, D, 0, Tl, B, dq_part, dkv_part, stream);
 }
 
 extern "C" int hept_block_attn_bwd_f32mfma(const float* qhat, const float* kvhat, const int32_t* qpos,
                                            const int32_t* kpos, const float* gacc, int N, int H, int D, int Tl, int B,
                                            float* dq_part, float* dkv_part, void* stream) {
-    return block_attn_bwd_impl(false, qhat, kvhat, qpos, kpos, gacc, N, H, D, Tl, B, dq_part, dkv_part, stream);
+    return block_attn_bwd_impl(BWD_F32MFMA, qhat, kvhat, qpos, kpos, gacc, N, H, D, 0, Tl, B, dq_part, dkv_part, stream);
+}
+
+extern "C" int hept_block_attn_bwd_diff(const float* qhat, const float* kvhat, const int32_t* qpos, const int32_t* kpos,
+                                        const float* gacc, int N, int H, int D, int C, int Tl, int B, float* dq_part,
+                                        float* dkv_part, void* stream) {
+    return block_attn_bwd_impl(BWD_DIFF, qhat, kvhat, qpos, kpos, gacc, N, H, D, C, Tl, B, dq_part, dkv_part, stream);
 }
 
 extern "C" int hept_block_attn_bwd_bf16(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,

@@ -17,7 +17,8 @@ checkpoints carry) and call ``forward`` with that variant's kwargs — ``raw_siz
 Two keyword-only extensions: ``precision`` ("fp32" reference numerics: f32 rows, tile products as split-bf16
 MFMAs accurate to f32 round-off / "fp32_mfma" the same on the native f32 MFMA, slower, kept as ground truth /
 "fp32_diff" = "fp32_mfma" with the coordinate part of the logit as explicit differences: the mode for a trained
-``w_rpe`` on un-normalised coordinates, where the reference's own fp32 logits are rounding noise /
+``w_rpe`` on un-normalised coordinates, where the reference's own fp32 logits are rounding noise; it trains in the
+same form (difference-form forward and backward, f32 tiles), so the forward is the same with and without grad /
 "bf16" MFMA tiles / "mixed16" = fp16 q̂,k̂ tiles with bf16 weights and values) and ``process_group`` (shard the ``n_hashes`` tables over
 the ranks of a ``torch.distributed`` group).
 
@@ -134,7 +135,7 @@ class HEPTAttention(nn.Module):
         ):
             # differentiable path (f32 tiles).  The usual ``model.eval(); model(x)`` without ``torch.no_grad()`` also
             # lands here because the parameters require grad: with fp32 tiles on one GPU it simply takes the autograd
-            # path (same values); with 16-bit tiles or table sharding an eval-mode call whose inputs carry no
+            # path (same values, "fp32_diff" included: its training forward is the difference form); with 16-bit tiles or table sharding an eval-mode call whose inputs carry no
             # gradient is served by the inference path instead, as the reference would serve it
             light = self.precision in ("fp32", "fp32_mfma", "fp32_diff") and self.sharding is None
             if light or self.training or any(t.requires_grad for t in (query, key, value)):
@@ -249,7 +250,11 @@ class HEPTAttention(nn.Module):
     def _train_tiles(self) -> str:
         if self.train_tiles not in ("fp32", "bf16"):
             raise ValueError("train_tiles must be 'fp32' or 'bf16'")
-        return "fp32" if self.precision == "fp32_mfma" else self.train_tiles
+        return "fp32" if self.precision in ("fp32_mfma", "fp32_diff") else self.train_tiles
+
+    def _train_f32_mfma(self):
+        """The ``f32_mfma`` argument of the training kernels, forward and backward: "diff" for ``precision="fp32_diff"``"""
+        return "diff" if self.precision == "fp32_diff" else self.precision == "fp32_mfma"
 
     def _train_fused_ok(self, x, kwargs) -> bool:
         """Whether the training-mode ``Attn`` block may hand its LayerNorm and projections to the fused row builder"""
@@ -276,7 +281,7 @@ class HEPTAttention(nn.Module):
         acc = HeptPartialSumsFused.apply(x.float(), norm1.weight.float(), norm1.bias.float(), norm1.eps, w_q.weight.float(),
                                          w_k.weight.float(), w_v.weight.float(), kwargs["coords"].float(), sqrt_w,
                                          self.e2lsh.alpha.detach(), codes, self.block_size,
-                                         self.precision == "fp32_mfma", self._train_tiles(), geo)
+                                         self._train_f32_mfma(), self._train_tiles(), geo)
         return HeptCombine.apply(acc, self.out_linear.weight, self.out_linear.bias).to(x.dtype)
 
     def _forward_train(self, query, key, value, **kwargs):
@@ -285,7 +290,7 @@ class HEPTAttention(nn.Module):
 
         # training runs f32 tiles -- also for a module whose inference precision is 16-bit -- so that the gradients are
         # those of the reference's fp32 arithmetic; `train_tiles = "bf16"` opts into the 16-bit kernels in both directions
-        f32_mfma = self.precision == "fp32_mfma"
+        f32_mfma = self._train_f32_mfma()
         tiles = self._train_tiles()
         n = query.shape[0]
         if n % self.block_size != 0:

@@ -382,7 +382,9 @@ def block_attn_bwd(qhat, kvhat, qpos, kpos, gacc, head_dim: int, coords_dim: int
                    f32_mfma: bool = False, coords: Optional[torch.Tensor] = None, raw_size: Optional[int] = None):
     """Backward of block_attn + reduce_tables for f32 (or bf16) tiles: gradient rows gacc (N,H,32) -> dq, dk, dv (N, H*D)
     and dcs (N, H, C), the gradient of the scaled coordinates shared by q^ and k^.  ``f32_mfma`` selects the
-    native f32 MFMA kernel instead of the split-bf16 products.  With ``coords`` (N, C) a fifth result
+    native f32 MFMA kernel instead of the split-bf16 products; ``f32_mfma="diff"`` its difference form (f32 rows only):
+    the logits as ``block_attn(..., f32_mfma="diff")`` forms them and the coordinate columns of the gradient summed as
+    differences, the backward of ``precision="fp32_diff"``.  With ``coords`` (N, C) a fifth result
     d_sqrt_w (H, C) = sum_n dcs * coords is reduced in the same pass; rows at and after ``raw_size`` get zeros."""
     lib = _lib.load()
     if qhat.dtype not in (torch.float32, torch.bfloat16):
@@ -390,6 +392,8 @@ def block_attn_bwd(qhat, kvhat, qpos, kpos, gacc, head_dim: int, coords_dim: int
     h, n, _ = qhat.shape
     tl = qpos.shape[0]
     gacc = _f32c(gacc, "grad of the partial sums")
+    qpos = qpos.to(torch.int32).contiguous()   # as block_attn takes them (a strided view would be read as if it were dense)
+    kpos = kpos.to(torch.int32).contiguous()
     dev = qhat.device
     rows16 = qhat.dtype == torch.bfloat16
     part_dtype = torch.bfloat16 if rows16 else torch.float32
@@ -400,8 +404,13 @@ def block_attn_bwd(qhat, kvhat, qpos, kpos, gacc, head_dim: int, coords_dim: int
         fn = lib.hept_block_attn_bwd_bf16
     else:
         fn = lib.hept_block_attn_bwd_f32mfma if f32_mfma else lib.hept_block_attn_bwd
-    _lib.check(fn(qhat.data_ptr(), kvhat.data_ptr(), qpos.data_ptr(), kpos.data_ptr(), gacc.data_ptr(), n, h, head_dim,
-                  tl, block_size, dq_part.data_ptr(), dkv_part.data_ptr(), st), "hept_block_attn_bwd")
+    dims = (n, h, head_dim, tl, block_size)
+    if not rows16 and isinstance(f32_mfma, str):
+        if f32_mfma != "diff":
+            raise ValueError(f"f32_mfma must be False, True or 'diff', got {f32_mfma!r}")
+        fn, dims = lib.hept_block_attn_bwd_diff, (n, h, head_dim, coords_dim, tl, block_size)
+    _lib.check(fn(qhat.data_ptr(), kvhat.data_ptr(), qpos.data_ptr(), kpos.data_ptr(), gacc.data_ptr(), *dims,
+                  dq_part.data_ptr(), dkv_part.data_ptr(), st), "hept_block_attn_bwd")
     dq = torch.empty(n, h * head_dim, device=dev, dtype=torch.float32)
     dk, dv = torch.empty_like(dq), torch.empty_like(dq)
     dcs = torch.empty(n, h, coords_dim, device=dev, dtype=torch.float32)

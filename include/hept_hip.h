@@ -463,6 +463,15 @@ int hept_block_attn_bwd(const float* qhat, const float* kvhat, const int32_t* qp
 int hept_block_attn_bwd_f32mfma(const float* qhat, const float* kvhat, const int32_t* qpos, const int32_t* kpos,
                                 const float* gacc, int N, int H, int D, int Tl, int B, float* dq_part,
                                 float* dkv_part, void* stream);
+/* the backward of HEPT_PREC_F32_DIFF, on the f32-MFMA kernel: the logits are recomputed as that forward forms them
+ * (feature columns through the MFMA, every coordinate column c in [D, D + C) as -(q^_c - k^_c)^2 / 2), and the
+ * coordinate columns of d q^ / d k^ are summed as sum_j dS_ij (k^_c[j] - q^_c[i]), not as Z - rowsum(dS) q^.  With a
+ * trained w_rpe on raw coordinates (sqrt_w ~ 5.8e3) the other two kernels recompute noise.  Same arguments and
+ * checks as its siblings plus C (1 <= C, D + C <= 30: HEPT_ERR_SHAPE otherwise); same dq_part / dkv_part rows, summed by
+ * hept_bwd_reduce.  C > 6 takes ceil(C / 6) launches. */
+int hept_block_attn_bwd_diff(const float* qhat, const float* kvhat, const int32_t* qpos, const int32_t* kpos,
+                             const float* gacc, int N, int H, int D, int C, int Tl, int B, float* dq_part,
+                             float* dkv_part, void* stream);
 /* the same on the rows of the bf16 forward (HEPT_PREC_BF16: qhat (H, N, 64 B), kvhat (H, N, 128 B)), one bf16 MFMA per
  * product: the opt-in 16-bit training mode.  The per-table gradient rows are bf16 as well: dq_part16 (Tl, N, H, 32) and
  * dkv_part16 (Tl, N, H, 64) of bf16; hept_bwd_reduce16 sums them (in f32) like hept_bwd_reduce. */

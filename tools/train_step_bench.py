@@ -1,5 +1,8 @@
 """fwd + bwd of HEPTAttention (autograd path) at tracking-60k: ms per training step with fp32 tiles (default) and with
-the opt-in bf16 tiles (``train_tiles = "bf16"``), and how far the bf16 gradients are from the fp32 ones."""
+the opt-in bf16 tiles (``train_tiles = "bf16"``), and how far the bf16 gradients are from the fp32 ones.
+
+``--precisions fp32,fp32_mfma,fp32_diff [--rounds 3]``: instead, the step time of each module precision (f32 training
+tiles), the precisions alternating in one process for the given number of rounds; prints every round and the median."""
 import os
 import sys
 import time
@@ -36,6 +39,31 @@ def grads():
     q.grad = k.grad = v.grad = w_rpe.weight.grad = m.out_linear.weight.grad = None
     return out.detach().clone(), res
 
+
+def timed(steps=30, warmup=5):
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+if "--precisions" in sys.argv:
+    precisions = sys.argv[sys.argv.index("--precisions") + 1].split(",")
+    rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 3
+    times = {p: [] for p in precisions}
+    for r in range(rounds):
+        for p in precisions:
+            m.precision = p
+            times[p].append(timed())
+            print(f"round {r} train step (fwd+bwd, precision {p}): {times[p][-1]:.3f} ms", flush=True)
+    for p in precisions:
+        print(f"train step (fwd+bwd, precision {p}): median {sorted(times[p])[len(times[p]) // 2]:.3f} ms, "
+              f"min {min(times[p]):.3f}, max {max(times[p]):.3f} over {rounds} rounds")
+    sys.exit(0)
 
 ref_out, ref = None, None
 for tiles in ("fp32", "bf16"):
