@@ -134,18 +134,26 @@ struct Row {
     }
 };
 
-// LayerNorm(24) of a row as torch computes it (biased variance, eps inside the root): xhat, and mean / rstd
+// LayerNorm(24) of a row as torch defines it (biased variance, eps inside the root): xhat and rstd.  The mean is taken
+// in two steps -- a shift c near the row's centre, then the mean m of the shifted row -- and the row is centred as
+// (x - c) - m: for a row whose values lie close together far from zero (mean 1e4, spread 1e-2) x - c is exact, where
+// x - mean with the one-step f32 mean is off by the round-off of a 24-term sum of the large values, as large as the
+// spread itself (xhat then missed float64 by 0.3; tests/dense_sweep.py "mean1e4").
 __device__ __forceinline__ void ln_stats(const Row& x, float eps, Row& xhat, float& rstd) {
-    float mean = 0.f;
+    float c = 0.f;
 #pragma unroll
-    for (int j = 0; j < BT_D; ++j) mean += x.v[j];
-    mean *= 1.0f / BT_D;
+    for (int j = 0; j < BT_D; ++j) c += x.v[j];
+    c *= 1.0f / BT_D;
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < BT_D; ++j) m += x.v[j] - c;
+    m *= 1.0f / BT_D;
     float var = 0.f;
 #pragma unroll
-    for (int j = 0; j < BT_D; ++j) { const float d = x.v[j] - mean; var = fmaf(d, d, var); }
+    for (int j = 0; j < BT_D; ++j) { const float d = (x.v[j] - c) - m; var = fmaf(d, d, var); }
     rstd = 1.0f / sqrtf(var * (1.0f / BT_D) + eps);
 #pragma unroll
-    for (int j = 0; j < BT_D; ++j) xhat.v[j] = (x.v[j] - mean) * rstd;
+    for (int j = 0; j < BT_D; ++j) xhat.v[j] = ((x.v[j] - c) - m) * rstd;
 }
 // d x of LayerNorm from d(xhat * w + b) = dz:  dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dz * w
 __device__ __forceinline__ void ln_backward(const Row& dz, const Row& xhat, float rstd, const float* __restrict__ w_s,

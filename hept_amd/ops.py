@@ -105,6 +105,23 @@ def _inc(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.clone() if t.data_ptr() % 16 else t
 
 
+def _rowsc(t: torch.Tensor, name: str) -> torch.Tensor:
+    """``_f32c`` for the row tensors the stage functions hand from one stage to the next -- f32 rows, hashes and hash
+    ranges, bf16 / f16 tiles, packed partial rows (int32): the kernels index them as dense arrays and move their rows as
+    16-byte pieces, so a strided view or a view at an odd storage offset gets a dense, aligned copy instead of being read
+    as if it were dense."""
+    if t.dtype is torch.float32:
+        return _f32c(t, name)
+    if t.dtype is not torch.int32:
+        return _inc(t, name)   # bfloat16 / float16 tiles (any other type is refused there)
+    if t.is_cuda and t.is_contiguous() and not (t.data_ptr() & 15):
+        return t
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (hept_amd has no CPU path); got device {t.device}")
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 def _qkv_in(q, k, v):
     """query, key, value as the C ABI takes them and their common HEPT_IN_* code; the three must share one dtype."""
     if not (q.dtype == k.dtype == v.dtype):
@@ -259,6 +276,7 @@ def prep_hash(q, k, v, coords, sqrt_w, alpha, codes, precision="fp32", t0: int =
 def sort_tables(qproj, kproj, codes, minmax, t0: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Stable ascending permutations (Tl,H,N) int32 of ``proj + float(code) * span`` for q and k."""
     lib = _lib.load()
+    qproj, kproj, minmax = _f32c(qproj, "qproj"), _f32c(kproj, "kproj"), _f32c(minmax, "minmax")
     tl, h, n = qproj.shape
     codes = _codes(codes, exc=TypeError)
     t = codes.shape[0]
@@ -274,6 +292,7 @@ def sort_tables(qproj, kproj, codes, minmax, t0: int = 0) -> Tuple[torch.Tensor,
 def sort_tables_src(qproj, kproj, eta_idx, phi_idx, cfac, minmax, t0: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """src-variant keys (hash + get_geo_shift): stable ascending permutations (Tl,H,N) int32 for q and k."""
     lib = _lib.load()
+    qproj, kproj, minmax = _f32c(qproj, "qproj"), _f32c(kproj, "kproj"), _f32c(minmax, "minmax")
     tl, h, n = qproj.shape
     eta_idx, phi_idx, cfac = (_f32c(x, nm) for x, nm in ((eta_idx, "region_indices[0]"), (phi_idx, "region_indices[1]"),
                                                           (cfac, "cfac")))
@@ -316,6 +335,7 @@ def block_attn(qhat, kvhat, qpos, kpos, head_dim: int, block_size: int, f32_mfma
     ``f32_mfma`` runs f32 tiles on the native f32 MFMA instead of the split-bf16 products; ``f32_mfma="diff"`` the
     difference form of the coordinate columns on top of that (``precision="fp32_diff"``)."""
     lib = _lib.load()
+    qhat, kvhat = _rowsc(qhat, "qhat"), _rowsc(kvhat, "kvhat")
     h, n, _ = qhat.shape
     tl = qpos.shape[0]
     prec = {torch.float32: PREC_F32, torch.bfloat16: PREC_BF16, torch.float16: PREC_MIXED16}[qhat.dtype]
@@ -353,6 +373,7 @@ def reduce_tables(part: torch.Tensor, head_dim: int = 24, packed: bool = False) 
     """Sum of the per-table partial rows: f32 rows (N,H,32), or with ``packed`` (packed input only) packed rows
     (N,H,16) int32 again -- the form table sharding sends over xGMI."""
     lib = _lib.load()
+    part = _rowsc(part, "part")
     tl, n, h, _ = part.shape
     if packed and part.dtype != torch.int32:
         raise TypeError("packed sums need packed partial rows (16-bit tiles with head_dim 24)")
@@ -366,6 +387,7 @@ def reduce_tables(part: torch.Tensor, head_dim: int = 24, packed: bool = False) 
 def combine_out(part: torch.Tensor, head_dim: int, out_weight, out_bias, n0: int = 0, n_count: Optional[int] = None) -> torch.Tensor:
     """(sum_t numer / sum_t denom) -> Linear(H*D -> D) for points [n0, n0+n_count); part is (Tl,N,H,row) or (N,H,32)."""
     lib = _lib.load()
+    part = _rowsc(part, "part")
     if part.dim() == 3:
         part = part.unsqueeze(0)
     tl, n, h, _ = part.shape
@@ -389,6 +411,7 @@ def block_attn_bwd(qhat, kvhat, qpos, kpos, gacc, head_dim: int, coords_dim: int
     lib = _lib.load()
     if qhat.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError("the backward pass needs f32 or bf16 tiles (rows of precision 'fp32' or 'bf16')")
+    qhat, kvhat = _rowsc(qhat, "qhat"), _rowsc(kvhat, "kvhat")
     h, n, _ = qhat.shape
     tl = qpos.shape[0]
     gacc = _f32c(gacc, "grad of the partial sums")
@@ -619,6 +642,7 @@ def combine_ffn(part: torch.Tensor, head_dim: int, out_weight, out_bias, x, norm
     same kernel; reference ``example/transformer.py:161-165`` in eval mode.  ``x`` is the full (N, D) block input, float32,
     bfloat16 or float16; the result has its dtype (the float32 result rounded once, as ``.to(x.dtype)`` rounds)."""
     lib = _lib.load()
+    part = _rowsc(part, "part")
     if part.dim() == 3:
         part = part.unsqueeze(0)
     tl, n, h, _ = part.shape
