@@ -151,9 +151,12 @@ __global__ __launch_bounds__(PT) void pad_gather_kernel(const int* __restrict__ 
     } else {
         // pad slot j - n_c copies the point at sorted position raw_end - B + (j - n_c) of the table-0/head-0
         // code order; a cloud smaller than B reaches into the previous cloud, a negative index wraps
-        // (torch indexing), exactly as the reference does
+        // (torch indexing), exactly as the reference does.  The reference wraps ONCE and raises IndexError when the
+        // index is still negative (first cloud + n_raw < B); callers refuse such a batch (hept_hip.h).  A batch that
+        // reaches this kernel all the same gets sorted position 0: never an index outside by_code
         int sp = cloud_start[c + 1] - B + (j - n_c);
         if (sp < 0) sp += n_raw;
+        if (sp < 0) sp = 0;
         src = by_code[sp];
     }
     const int part = blockIdx.y;
@@ -310,7 +313,10 @@ __global__ __launch_bounds__(256) void probe_kernel(const void* __restrict__ bat
         host[1] = run;                                  // n_pad
         host[2] = longest;
         host[3] = smallest;                             // < 1: a cloud id without points
-        host[4] = edge_s[PROBE_CLOUDS] < n_raw ? 1 : 0; // more clouds than the probe resolves
+        // bit 0: more clouds than the probe resolves; bit 1: the first cloud's pad window starts more than n_raw
+        // positions in front of the batch (size0 + n_raw < B): the reference's IndexError, refused by the caller
+        const int size0 = edge_s[1] - edge_s[0];
+        host[4] = (edge_s[PROBE_CLOUDS] < n_raw ? 1 : 0) | (size0 + n_raw < B ? 2 : 0);
         host[5] = __float_as_int(m0);
         host[6] = __float_as_int(m1);
         host[7] = 0x600DF00D;                           // written last: the record is complete
@@ -362,6 +368,10 @@ extern "C" int hept_prepare_input(const float* coords, int C, const int32_t* clo
         return HEPT_ERR_ARG;
     if (C < 2 || n_clouds < 1 || n_raw < 1 || max_cloud < 1 || n_pad < n_raw || T < 1 || H < 1 || B < 1)
         return HEPT_ERR_SHAPE;
+    // the pad window of the first cloud may wrap once (size0 + n_raw >= B).  The sizes are device data; what the host
+    // arguments decide: size0 <= n_raw - (n_clouds - 1), so a batch below that bound breaks the rule whatever its
+    // clouds are (exact for one cloud).  The rest is the caller's precondition; pad_gather_kernel clamps
+    if ((long long)2 * n_raw - (n_clouds - 1) < (long long)B) return HEPT_ERR_SHAPE;
     if (workspace_bytes < hept_prepare_workspace_bytes(n_raw, n_clouds, max_cloud, T, H)) return HEPT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int S = 2 * n_clouds, L = max_cloud, rows = T * H;

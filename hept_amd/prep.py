@@ -106,6 +106,12 @@ def _rank_within_cloud(values: torch.Tensor, batch: torch.Tensor, raw_start: tor
 
 
 _MAX_CLOUDS_ONE_TRIP = 255
+# The pad slots of the first cloud copy sorted positions size0 - block_size + j; a negative position wraps once (torch
+# indexing), and the reference raises IndexError when it lies more than n_raw in front of the batch.  The CPU mirror
+# raises there as well (its gather is the same torch indexing); the GPU front end refuses before it launches or
+# allocates anything.
+_WRAP_MESSAGE = ("the first cloud's padding would index more than n_raw = {n_raw} positions in front of the batch "
+                 "(first cloud + n_raw < block_size = {block_size}); the reference raises IndexError here as well")
 
 
 def prepare_input_hip(x, coords, batch, helper_params) -> Tuple[torch.Tensor, Dict[str, torch.Tensor], torch.Tensor]:
@@ -150,7 +156,7 @@ def prepare_input_hip(x, coords, batch, helper_params) -> Tuple[torch.Tensor, Di
         rec = record.tolist()
         if rec[7] != 0x600DF00D:
             raise RuntimeError("hept_prepare_probe: the host record was not written")
-        if not rec[4]:
+        if not rec[4] & 1:
             n_clouds, n_pad, max_cloud, smallest = rec[0], rec[1], rec[2], rec[3]
             if smallest < 1:
                 raise ValueError("every cloud id in [0, batch.max()] must own at least one point")
@@ -158,6 +164,8 @@ def prepare_input_hip(x, coords, batch, helper_params) -> Tuple[torch.Tensor, Di
             bits = sum((int(math.ceil(float(v))) + 1).bit_length() for v in reg_hi)
             if (n_clouds << bits) >= (1 << 24):
                 raise ValueError("AND codes would exceed 2^24: too many clouds x regions for the fp32-keyed pad sort")
+            if rec[4] & 2:
+                raise IndexError(_WRAP_MESSAGE.format(block_size=block_size, n_raw=n_raw))
             return _prepare_outputs(lib, x, coords, coords_c, c_dim, bounds[:257], bounds[257:], n_clouds, n_raw,
                                     max_cloud, n_pad, regions, n_tables, num_heads, block_size, stream)
     probe = _MAX_CLOUDS_ONE_TRIP
@@ -182,6 +190,8 @@ def prepare_input_hip(x, coords, batch, helper_params) -> Tuple[torch.Tensor, Di
     bits = sum((int(math.ceil(float(host[n_clouds + 1 + a]))) + 1).bit_length() for a in (0, 1))
     if (n_clouds << bits) >= (1 << 24):
         raise ValueError("AND codes would exceed 2^24: too many clouds x regions for the fp32-keyed pad sort")
+    if int(sizes[0]) + n_raw < block_size:
+        raise IndexError(_WRAP_MESSAGE.format(block_size=block_size, n_raw=n_raw))
     pad_start = torch.cat([torch.zeros(1, dtype=torch.int64), padded.cumsum(0)]).to(torch.int32).to(dev, non_blocking=True)
     return _prepare_outputs(lib, x, coords, coords_c, c_dim, cloud_start, pad_start, n_clouds, n_raw, max_cloud, n_pad,
                             regions, n_tables, num_heads, block_size, stream)
@@ -205,7 +215,10 @@ def _prepare_outputs(lib, x, coords, coords_c, c_dim, cloud_start, pad_start, n_
                                       block_size, ws.data_ptr(), ws.numel(), pad_seq.data_ptr(), unpad.data_ptr(),
                                       coords_pad.data_ptr(), codes_pad.data_ptr(), stream.cuda_stream),
                "hept_prepare_input")
-    kwargs = {"combined_shifts": codes_pad, "coords": coords_pad.to(coords.dtype)}
+    # the kernel gathered the float32 rounding of the coordinates; a caller with another dtype gets its own values
+    # back (float64 would otherwise return rounded): kwargs["coords"] is coords[pad_seq] bit for bit, as in the reference
+    coords_out = coords_pad if coords.dtype == torch.float32 else coords[pad_seq]
+    kwargs = {"combined_shifts": codes_pad, "coords": coords_out}
     return x[pad_seq], kwargs, unpad.bool()
 
 

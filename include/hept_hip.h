@@ -510,13 +510,21 @@ int hept_combine_bwd(const float* acc, const float* g_out, const float* out_weig
  *   block-padded cloud sizes; regions (T, 2, H) f32; max_cloud = largest raw cloud; n_pad = pad_start[n_clouds].
  * Outputs: pad_seq (n_pad) i64, unpad (n_pad) u8 mask, coords_pad (n_pad, C) f32, codes_pad (T, H, n_pad) i64.
  * Ties (equal coordinates / equal codes) are broken by ascending index; the reference's argsort leaves them
- * undefined.  Requires every packed code < 2^24. */
+ * undefined.  Requires every packed code < 2^24.
+ * PAD WINDOW RULE: pad slot j of cloud i copies sorted position cloud_start[i + 1] - B + j of the table-0 / head-0
+ * code order; a negative position wraps once (+ n_raw), as torch indexing does in the reference.  The reference raises
+ * IndexError when the position is still negative, that is when (size of cloud 0) + n_raw < B.  The caller must refuse
+ * such a batch (hept_prepare_probe reports it; hept_amd.prep raises IndexError).  hept_prepare_input itself refuses
+ * with HEPT_ERR_SHAPE what its host arguments decide, 2 * n_raw - (n_clouds - 1) < B (exact for one cloud); for the
+ * rest the kernel clamps the position to 0, so no index leaves the sorted order, but the pads are then not the
+ * reference's (it has none). */
 size_t hept_prepare_workspace_bytes(int n_raw, int n_clouds, int max_cloud, int T, int H);
 /* The host round trip in front of hept_prepare_input (example/transformer.py:35-43 synchronises on the cloud sizes as
  * well): one small kernel reads the sorted batch vector (i64 or i32, n_raw entries, cloud ids 0 .. n_clouds - 1) and
  * regions (T, 2, H), leaves cloud_start / pad_start (257 i32 each, device) for hept_prepare_input and writes a record
  * of 8 i32 into pinned host memory: [n_clouds, n_pad, longest cloud, smallest cloud (< 1: a cloud id without points),
- * overflow (more than 255 clouds: not resolved, use another path), f32 bits of the largest region count of axis 0,
+ * flags (bit 0: more than 255 clouds, not resolved, use another path; bit 1: cloud 0 + n_raw < B, the pad window rule
+ * below is broken: refuse the batch), f32 bits of the largest region count of axis 0,
  * of axis 1, 0x600DF00D].  The caller synchronises the stream and reads the record.
  * HARD PRECONDITION: host_record is pinned, device-mapped host memory (hipHostMalloc / hipHostRegister); ordinary
  * pageable memory is refused with HEPT_ERR_ARG (a kernel store to it would be a GPU fault, not an error code). */

@@ -168,3 +168,25 @@ def test_base_call_has_valid_sizes(lib):
 def test_refused_with_the_recorded_code(lib, fault, entry):
     _, overrides, code, _ = CASES[fault]
     assert call(lib, entry, overrides) == code
+
+
+def test_prepare_input_refuses_a_pad_window_before_the_batch(lib):
+    """hept_prepare_input: pad positions wrap once, and the first cloud's may not start more than n_raw in front of the
+    batch (cloud 0 + n_raw >= B, include/hept_hip.h).  The cloud sizes are device data; what the host arguments decide,
+    2 * n_raw - (n_clouds - 1) < B, is refused with HEPT_ERR_SHAPE before any HIP call.  EVERY call carries a 16-byte
+    workspace: the size checks come first, and a call that passes them is refused for its workspace (HEPT_ERR_ARG), so
+    nothing is ever launched on the dummy pointers, whatever the rule decides."""
+    def call_prepare(n_clouds, n_raw, max_cloud, n_pad, b):
+        return lib.hept_prepare_input(PTR, 3, PTR, PTR, n_clouds, n_raw, max_cloud, n_pad, PTR, 2, 3, b, PTR, 16, PTR,
+                                      PTR, PTR, PTR, None)
+
+    assert call_prepare(1, 10, 10, 64, 64) == SHAPE            # one cloud of 10, B = 64: 10 + 10 < 64
+    assert call_prepare(1, 31, 31, 64, 64) == SHAPE            # 31 + 31 < 64
+    assert call_prepare(1, 32, 32, 64, 64) == ARG              # 32 + 32 == 64: legal
+    assert call_prepare(2, 8, 4, 32, 16) == SHAPE              # two clouds, 8 points: at most 7 + 8 < 16
+    assert call_prepare(300, 300, 1, 300000, 1000) == SHAPE    # 300 clouds of 1, B = 1000
+    # clouds (5, 5) or (1, 12) with B = 16 break the rule (5 + 10, 1 + 13 < 16), but (9, 1) and (12, 1) would not: the
+    # host arguments cannot tell, the caller must (hept_prepare_probe's flag; hept_amd.prep raises IndexError), and the
+    # kernel clamps
+    assert call_prepare(2, 10, 5, 32, 16) == ARG
+    assert call_prepare(2, 13, 12, 32, 16) == ARG
