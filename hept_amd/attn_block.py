@@ -85,6 +85,14 @@ class Attn(nn.Module):
     def forward(self, x, kwargs):
         if not self._fused_ok(x):
             # reference composition, example/transformer.py:154-165 (training: dropout + autograd)
+            # gradient-enabled calls on 16-bit activations (what torch.autocast hands the block): widened once here, the
+            # result narrowed once at the end, as the one-call eval block does: y = block(x.float()).to(x.dtype).  Left in 16 bits, the
+            # residual adds and norm2 / ff would run on rounded rows (or refuse the float32 parameters outright) and the
+            # LnFfn node would be skipped
+            narrow = (x.dtype if x.is_cuda and torch.is_grad_enabled() and x.dtype in (torch.bfloat16, torch.float16)
+                      else None)
+            if narrow is not None:
+                x = x.float()
             if self.fuse_training and torch.is_grad_enabled() and self.attn._train_fused_ok(x, kwargs):
                 # the same composition with norm1 / w_q / w_k / w_v folded into the operator's row builder: q, k, v
                 # never exist in HBM, gradients reach the same parameters (autograd.HeptPartialSumsFused)
@@ -103,7 +111,8 @@ class Attn(nn.Module):
                                         self.ff[0].bias, self.ff[2].weight, self.ff[2].bias)
             else:
                 ff_output = self.ff(self.norm2(x))
-            return x + self.dropout(ff_output)
+            y = x + self.dropout(ff_output)
+            return y if narrow is None else y.to(narrow)
         a = self.attn
         src = a.variant == "src"
         # the one-call block reads and writes these three natively; anything else (float64) is widened / narrowed in torch

@@ -10,12 +10,34 @@ differentiable parameter math around it (``sqrt_w`` from ``w_rpe.weight``, the f
 """
 from __future__ import annotations
 
+import functools
+
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
+
 __all__ = ["HeptPartialSums", "HeptPartialSumsFused", "HeptCombine", "LnFfn", "RpeScale", "rpe_scale_torch", "ReplicatedGrad",
            "sum_over_ranks"]
+
+
+def _first_order_only(backward):
+    """Every backward here is HIP kernels behind ctypes calls, which record no graph: a second derivative through one
+    would be that of its few torch tails only (``dcs * sqrt_w``, ``dq @ w_q``) -- a wrong number, not an error.  So a
+    backward refuses ``create_graph=True`` (the engine runs it in grad mode only then) outright, also where the incoming
+    gradient carries no graph and ``once_differentiable`` alone would hand back constants without a word (the composed
+    block, whose torch LayerNorm would then be differentiated around a frozen operator)."""
+    once = once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def refuse_second_order(ctx, *grads):
+        if torch.is_grad_enabled():
+            raise RuntimeError("hept_amd: the backward of the HIP training path is not differentiable (create_graph=True "
+                               "/ double backward): gradient penalties through the operator are not supported")
+        return once(ctx, *grads)
+
+    return refuse_second_order
 
 
 class ReplicatedGrad(torch.autograd.Function):
@@ -28,6 +50,7 @@ class ReplicatedGrad(torch.autograd.Function):
         return x.view_as(x)
 
     @staticmethod
+    @_first_order_only
     def backward(ctx, g):
         import torch.distributed as dist
 
@@ -49,6 +72,7 @@ class _SumOverRanks(torch.autograd.Function):
         return y
 
     @staticmethod
+    @_first_order_only
     def backward(ctx, g):
         return g, None
 
@@ -76,6 +100,7 @@ class RpeScale(torch.autograd.Function):
         return ops.rpe_scale(w_rpe_weight, n_heads, head_dim, w_per_dist)
 
     @staticmethod
+    @_first_order_only
     def backward(ctx, d_sqrt_w):
         (w,) = ctx.saved_tensors
         h, d, k = ctx.dims
@@ -131,6 +156,7 @@ class HeptPartialSums(torch.autograd.Function):
         return acc
 
     @staticmethod
+    @_first_order_only
     def backward(ctx, gacc):
         qhat, kvhat, qpos, kpos, coords, sqrt_w = ctx.saved_tensors
         d, c, block_size = ctx.dims
@@ -198,6 +224,7 @@ class HeptPartialSumsFused(torch.autograd.Function):
         return acc
 
     @staticmethod
+    @_first_order_only
     def backward(ctx, gacc):
         qhat, kvhat, qpos, kpos, coords, sqrt_w, x, ln_w, ln_b, w_q, w_k, w_v = ctx.saved_tensors
         d, c, block_size, eps = ctx.dims
@@ -232,6 +259,7 @@ class HeptCombine(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_first_order_only
     def backward(ctx, g_out):
         acc, weight = ctx.saved_tensors
         gacc, dw, db = ops.combine_bwd(acc, g_out.contiguous(), weight, need_bias=ctx.has_bias)
@@ -250,6 +278,7 @@ class LnFfn(torch.autograd.Function):
         return ops.ln_ffn_fwd(x1, ln_w, ln_b, eps, w1, b1, w2, b2)
 
     @staticmethod
+    @_first_order_only
     def backward(ctx, d_out):
         x1, ln_w, ln_b, w1, b1, w2, b2 = ctx.saved_tensors
         dx1, dlw, dlb, dw1, db1, dw2, db2 = ops.ln_ffn_bwd(x1, d_out.contiguous(), ln_w, ln_b, ctx.eps, w1, b1, w2, b2)

@@ -131,14 +131,16 @@ class HEPTAttention(nn.Module):
         if not query.is_cuda:
             raise RuntimeError("hept_amd.HEPTAttention needs GPU tensors: there is no CPU fallback")
         if torch.is_grad_enabled() and any(
-            t.requires_grad for t in (query, key, value, kwargs["w_rpe"].weight, self.out_linear.weight)
+            t.requires_grad for t in (query, key, value, kwargs["coords"], kwargs["w_rpe"].weight,
+                                      self.out_linear.weight, self.out_linear.bias)
         ):
-            # differentiable path (f32 tiles).  The usual ``model.eval(); model(x)`` without ``torch.no_grad()`` also
+            # differentiable path (f32 tiles): any of the seven tensors the reference differentiates, out_linear.bias
+            # and the coordinates (they enter q^ and k^) included.  The usual ``model.eval(); model(x)`` without ``torch.no_grad()`` also
             # lands here because the parameters require grad: with fp32 tiles on one GPU it simply takes the autograd
             # path (same values, "fp32_diff" included: its training forward is the difference form); with 16-bit tiles or table sharding an eval-mode call whose inputs carry no
             # gradient is served by the inference path instead, as the reference would serve it
             light = self.precision in ("fp32", "fp32_mfma", "fp32_diff") and self.sharding is None
-            if light or self.training or any(t.requires_grad for t in (query, key, value)):
+            if light or self.training or any(t.requires_grad for t in (query, key, value, kwargs["coords"])):
                 return self._forward_train(query, key, value, **kwargs)
             if not self._warned_eval_grad:
                 import warnings
