@@ -13,7 +13,7 @@ from ctypes import c_float, c_int, c_int64, c_size_t, c_void_p
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libhept_hip.so")
 
 ABI_VERSION = 22
-PREC_F32, PREC_BF16, PREC_MIXED16, PREC_F32_MFMA, PREC_F32_DIFF = 0, 1, 2, 3, 4
+PREC_F32, PREC_BF16, PREC_MIXED16, PREC_F32_MFMA, PREC_F32_DIFF, PREC_MIXED16_DIFF = 0, 1, 2, 3, 4, 5
 IN_F32, IN_BF16, IN_F16 = 0, 1, 2   # HEPT_IN_*: element type of q, k, v at the *_in entry points, of x and y at the *_io ones
 ROW = 32
 MAX_TABLES = 8
@@ -45,6 +45,7 @@ SIGNATURES = {
     "hept_segmented_argsort": (c_int, [_P, c_int, c_int, _P, _P, _P]),
     "hept_block_attn": (c_int, [_P] * 4 + [c_int] * 6 + [_P, _P]),
     "hept_block_attn_heads": (c_int, [_P] * 4 + [c_int] * 11 + [_P, _P]),
+    "hept_block_attn_coords": (c_int, [_P] * 6 + [c_int] * 7 + [_P, _P]),
     "hept_part_precision": (c_int, [c_int, c_int]),
     "hept_reduce_heads": (c_int, [_P] + [c_int] * 8 + [_P, c_int, _P]),
     "hept_combine_groups": (c_int, [_P] + [c_int] * 8 + [c_size_t] + [_P] * 4),

@@ -26,6 +26,8 @@
 // bf16 path: v_mfma_f32_32x32x16_bf16, V fragments by ds_read_b64_tr_b16 (mixed16: the K^.Q^T product
 // takes fp16 rows through v_mfma_f32_32x32x16_f16; P.V stays bf16 for the exponent range of tiny weights).
 // fp32 path: v_mfma_f32_32x32x2_f32 (exact fp32 fma chain), plain ds_read_b32 for V.
+// mixed16_diff (HEPT_PREC_MIXED16_DIFF): the mixed16 rows with the coordinate part of the logit in f32 -- a sibling kernel in
+// block_attn_coords.hip, dispatched from block_attn_impl below.
 // blockIdx % H = head: with H = 8 every XCD (round-robin dispatch) gathers from one head's
 // qhat/kvhat slab only (speed only; nothing depends on placement).
 #include "common.h"
@@ -763,7 +765,7 @@ int launch_attn(int nkt, dim3 grid, hipStream_t st, const char* qhat, const char
 namespace {
 int block_attn_impl(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos, int N, int H, int D,
                     int Tl, int B, int precision, const HeadRange& hr_in, float* part, void* stream,
-                    const PushArgs* push = nullptr, VSrc vs = VSrc{}) {
+                    const PushArgs* push = nullptr, VSrc vs = VSrc{}, const CoordSrc* cs = nullptr) {
     HeadRange hr = hr_in;
     hr.vsrc = nullptr;
     hr.raw_size = N;
@@ -824,6 +826,15 @@ int block_attn_impl(const void* qhat, const void* kvhat, const int32_t* qpos, co
         }
         return launch_attn<false, false, false, true>(nkt, grid, st, qh, kv, qpos, kpos, part, N, H, D, B, nb, hr, pa);
     }
+    if (precision == HEPT_PREC_MIXED16_DIFF) {
+        // block_attn_coords.hip.  A caller without coordinates (hept_block_attn, hept_block_attn_heads) has no such mode;
+        // neither has table sharding (no push workgroups, no direct scatter)
+        if (!cs || push) return HEPT_ERR_SHAPE;
+        if (!cs->coords || !cs->sqrt_w || !part) return HEPT_ERR_ARG;
+        if (cs->C < 2 || D + cs->C > 30 || cs->raw_size < 0 || cs->raw_size > N) return HEPT_ERR_SHAPE;
+        return hept_block_attn_coords_launch(qhat, kvhat, qpos, kpos, cs->coords, cs->sqrt_w, cs->raw_size, N, H, D, cs->C, Tl,
+                                             B, hr, part, stream);
+    }
     return HEPT_ERR_SHAPE;
 }
 }  // namespace
@@ -831,10 +842,20 @@ int block_attn_impl(const void* qhat, const void* kvhat, const int32_t* qpos, co
 // internal: hept_block_attn_heads whose launch also carries the one-sided push of another head group (comm.h)
 int hept_block_attn_heads_push(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos, int N,
                                int H, int D, int Tl, int B, int precision, int h0, int hg, int hout, int hsub,
-                               int n_rows_out, float* part, const PushArgs* push, void* stream, VSrc vs) {
+                               int n_rows_out, float* part, const PushArgs* push, void* stream, VSrc vs,
+                               const CoordSrc* cs) {
     if (n_rows_out < N) return HEPT_ERR_SHAPE;
     const HeadRange hr{h0, hg, hout, hsub, (long long)n_rows_out * hout, nullptr, 0, 0};
-    return block_attn_impl(qhat, kvhat, qpos, kpos, N, H, D, Tl, B, precision, hr, part, stream, push, vs);
+    return block_attn_impl(qhat, kvhat, qpos, kpos, N, H, D, Tl, B, precision, hr, part, stream, push, vs, cs);
+}
+
+extern "C" int hept_block_attn_coords(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,
+                                      const float* coords, const float* sqrt_w, int raw_size, int N, int H, int D, int C,
+                                      int Tl, int B, float* part, void* stream) {
+    if (!coords || !sqrt_w) return HEPT_ERR_ARG;
+    const HeadRange all{0, H, H, 0, (long long)N * H, nullptr, 0, 0};
+    const CoordSrc cs{coords, sqrt_w, C, raw_size};
+    return block_attn_impl(qhat, kvhat, qpos, kpos, N, H, D, Tl, B, HEPT_PREC_MIXED16_DIFF, all, part, stream, nullptr, VSrc{}, &cs);
 }
 
 extern "C" int hept_block_attn(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos, int N,

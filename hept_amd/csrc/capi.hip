@@ -18,6 +18,7 @@ struct Workspace {
     int32_t* pos_chunk;  // Tl > HEPT_MAX_TABLES only: (2, chunk, H, N) the sort of one chunk writes before it is filed
     void* sort_ws;
     float* part;    // (Tl, N, H, 32)
+    float* sqrt_w;  // HEPT_PREC_MIXED16_DIFF only: (H, C) f32, the scale the block attention reads (written on every call)
     size_t bytes;
 };
 
@@ -45,6 +46,8 @@ Workspace carve(void* base, int N, int H, int C, int Tl, int precision) {
     w.pos_chunk = Tl > Tc ? reinterpret_cast<int32_t*>(take((size_t)2 * Tc * H * N * 4)) : nullptr;
     w.sort_ws = take(hept_sort_workspace_bytes(N, H, Tc));
     w.part = reinterpret_cast<float*>(take((size_t)Tl * N * H * 32 * 4));
+    // (last, so that every other region lies where it lies for HEPT_PREC_MIXED16)
+    w.sqrt_w = precision == HEPT_PREC_MIXED16_DIFF ? reinterpret_cast<float*>(take((size_t)H * C * 4)) : nullptr;
     w.bytes = off;
     return w;
 }
@@ -142,10 +145,25 @@ int open_call(bool pointers, int dtype, const Sizes& s, int then, void* workspac
     return workspace_bytes < w->bytes ? HEPT_ERR_ARG : HEPT_OK;
 }
 
+// `then` of the table-sharded calls: HEPT_PREC_MIXED16_DIFF is not sharded (its block attention has no push path)
+inline int sharded_check(const Sizes& s) { return s.precision == HEPT_PREC_MIXED16_DIFF ? HEPT_ERR_SHAPE : HEPT_OK; }
+
 // `then` of the calls that hand out table sums: as f32 rows, or in the format the block attention writes them
 inline int acc_check(int acc_precision, const Sizes& s) {
+    if (sharded_check(s)) return HEPT_ERR_SHAPE;
     const bool ok = acc_precision == HEPT_PREC_F32 || acc_precision == hept_part_precision(s.precision, s.D);
     return ok ? HEPT_OK : HEPT_ERR_SHAPE;
+}
+
+// HEPT_PREC_MIXED16_DIFF: the (H, C) scale the block attention reads.  K == 0: the caller's sqrt_w as it stands; K > 0: the
+// weight math of the row builder's prologue once more, into the workspace's record, on every call (nothing derived from
+// a parameter is remembered) -- one 1-workgroup launch in front of the block attention, 7-8 us back to back
+// (profiles/mixed16_diff_bench.txt), instead of a new argument of the three row builders' prologues
+int coord_scale(const float* w_rpe, const Sizes& s, const Workspace& w, void* stream, const float** sqrt_w) {
+    *sqrt_w = w_rpe;
+    if (s.precision != HEPT_PREC_MIXED16_DIFF || s.K == 0) return HEPT_OK;
+    *sqrt_w = w.sqrt_w;
+    return hept_rpe_scale(w_rpe, s.H, s.D, s.C, s.K, w.sqrt_w, stream);
 }
 
 // The walk over tables [s.t0, s.t0 + s.Tl) in chunks of at most HEPT_MAX_TABLES: rows + hashes, then the sort, chunk by
@@ -233,8 +251,14 @@ int run_tables(const Inputs& in, const Sizes& s, const Workspace& w, float* part
     VSrc dv;
     int rc = run_begin(in, s, w, stream, direct_v_pays(s.B) ? &dv : nullptr);
     if (rc) return rc;
+    // (HEPT_PREC_MIXED16_DIFF: the block attention also reads the caller's coords and the scale; the row builder has
+    //  refused a bad K by now)
+    CoordSrc cs{in.coords, nullptr, s.C, in.geo.eta ? in.geo.raw_size : s.N};
+    rc = coord_scale(in.w_rpe, s, w, stream, &cs.sqrt_w);
+    if (rc) return rc;
     rc = hept_block_attn_heads_push(w.qhat, w.kvhat, w.pos, w.pos + (size_t)s.Tl * s.H * s.N, s.N, s.H, s.D, s.Tl, s.B,
-                                    s.precision, 0, s.H, s.H, 0, s.N, part, nullptr, stream, dv);
+                                    s.precision, 0, s.H, s.H, 0, s.N, part, nullptr, stream, dv,
+                                    s.precision == HEPT_PREC_MIXED16_DIFF ? &cs : nullptr);
     prof_mark(3, (hipStream_t)stream);
     return rc;
 }
@@ -301,8 +325,8 @@ int forward_partial_impl(const Inputs& in, const Sizes& s, int acc_precision, vo
 
 int partial_begin_impl(const Inputs& in, const Sizes& s, void* workspace, size_t workspace_bytes, void* stream) {
     Workspace w;
-    const int rc = open_call(in.q && in.k && in.v && in.coords && in.w_rpe && in.alpha && workspace, in.in_dtype, s, HEPT_OK,
-                             workspace, workspace_bytes, &w);
+    const int rc = open_call(in.q && in.k && in.v && in.coords && in.w_rpe && in.alpha && workspace, in.in_dtype, s,
+                             sharded_check(s), workspace, workspace_bytes, &w);
     return rc ? rc : run_begin(in, s, w, stream);
 }
 }  // namespace
@@ -632,7 +656,7 @@ int forward_sharded_impl(hept_comm* comm, const Inputs& in, const float* out_wei
     if (!out_full && !(one_sided && comm->out_view)) return HEPT_ERR_ARG;
     if (!one_sided && (transport != HEPT_TRANSPORT_RCCL || !xbuf)) return HEPT_ERR_ARG;
     const int then = (head_groups < 1 || head_groups > HEPT_MAX_HEAD_GROUPS || s.H % head_groups != 0 || s.K < 0 ||
-                      (s.K > 0 && s.H * (s.C - 1) * s.K > 1024)) ? HEPT_ERR_SHAPE : HEPT_OK;
+                      (s.K > 0 && s.H * (s.C - 1) * s.K > 1024)) ? HEPT_ERR_SHAPE : sharded_check(s);
     Workspace w;
     int rc = open_call(true, in.in_dtype, s, then, workspace, workspace_bytes, &w);
     if (rc) return rc;
@@ -723,8 +747,16 @@ int attn_block_impl(const void* x, int io_dtype, int ldx, const float* coords, c
                                         s.precision, w.qhat, w.kvhat, w.qproj, w.kproj, w.minmax, stream, zptr, zbytes);
     });
     if (rc) return rc;
-    rc = hept_block_attn(w.qhat, w.kvhat, w.pos, w.pos + (size_t)s.T * s.H * s.N, s.N, s.H, s.D, s.T, s.B, s.precision,
-                         w.part, stream);
+    if (s.precision == HEPT_PREC_MIXED16_DIFF) {   // the coordinates and the scale go to the kernel as well
+        CoordSrc cs{coords, nullptr, s.C, raw_size};
+        rc = coord_scale(p->w_rpe, s, w, stream, &cs.sqrt_w);
+        if (rc) return rc;
+        rc = hept_block_attn_heads_push(w.qhat, w.kvhat, w.pos, w.pos + (size_t)s.T * s.H * s.N, s.N, s.H, s.D, s.T, s.B,
+                                        s.precision, 0, s.H, s.H, 0, s.N, w.part, nullptr, stream, VSrc{}, &cs);
+    } else {
+        rc = hept_block_attn(w.qhat, w.kvhat, w.pos, w.pos + (size_t)s.T * s.H * s.N, s.N, s.H, s.D, s.T, s.B, s.precision,
+                             w.part, stream);
+    }
     if (rc) return rc;
     prof_mark(3, st);
     rc = hept_combine_ffn_ld(w.part, hept_part_precision(s.precision, s.D), s.T, s.N, s.H, s.D, 0, s.N, p->out_w, p->out_b,

@@ -32,6 +32,14 @@ struct VSrc {
     const float* v = nullptr;
     int raw_size = 0;
 };
+// HEPT_PREC_MIXED16_DIFF: what the block attention needs beside the 16-bit rows -- the caller's coords (N, C), sqrt_w (H, C)
+// and the src variant's raw_size (N: no padding rows).  Every other precision passes none.
+struct CoordSrc {
+    const float* coords = nullptr;
+    const float* sqrt_w = nullptr;
+    int C = 0;
+    int raw_size = 0;
+};
 
 // The q^ / k^|v rows of this precision hold f32 elements: "fp32" and the two modes that run other block-attention
 // kernels on the same rows.  The one spelling of that set: a new f32-row mode is added here and nowhere else.
@@ -298,5 +306,9 @@ void hept_sort_zero_block(void* sort_ws, int N, int H, int Tl, void** ptr, size_
 void hept_prof_mark_sort_mid(void* stream);
 // hept_segmented_argsort for a caller that knows finite bounds of its keys (prepare.hip: packed code keys): the
 // per-segment range pass (a fill and a kernel) is skipped; any bounds give the exact stable sort
+// the launch behind HEPT_PREC_MIXED16_DIFF (block_attn_coords.hip); arguments checked by block_attn.hip's block_attn_impl
+int hept_block_attn_coords_launch(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,
+                                  const float* coords, const float* sqrt_w, int raw_size, int N, int H, int D, int C, int Tl,
+                                  int B, const HeadRange& hr, float* part, void* stream);
 int hept_segmented_argsort_bounded(const float* keys, int S, int L, float lo, float hi, void* ws, int32_t* pos,
                                    void* stream);

@@ -851,6 +851,7 @@ int hept_prep_hash_rpe(const void* q, const void* k, const void* v, const float*
     if (H < 1 || H > 16 || D < 1 || D > 28 || C < 1 || D + C > 30) return HEPT_ERR_SHAPE;
     if (N < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
     if (hept_f32_rows(precision)) precision = HEPT_PREC_F32;  // same f32 tile rows, another block_attn kernel
+    if (precision == HEPT_PREC_MIXED16_DIFF) precision = HEPT_PREC_MIXED16;  // the mixed16 rows, another block_attn kernel
     if (precision != HEPT_PREC_F32 && precision != HEPT_PREC_BF16 && precision != HEPT_PREC_MIXED16)
         return HEPT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
@@ -914,6 +915,7 @@ int hept_prep_hash_fused_rpe(const void* x, int io_dtype, int ldx, const float* 
     // (contiguous f32 rows: the contract is unchanged; 16-bit rows are refused at any pitch)
     if ((ldx != D || io16) && (reinterpret_cast<uintptr_t>(x) & 15)) return HEPT_ERR_ARG;
     if (hept_f32_rows(precision)) precision = HEPT_PREC_F32;  // same f32 tile rows, another block_attn kernel
+    if (precision == HEPT_PREC_MIXED16_DIFF) precision = HEPT_PREC_MIXED16;  // the mixed16 rows, another block_attn kernel
     if (precision != HEPT_PREC_F32 && precision != HEPT_PREC_BF16 && precision != HEPT_PREC_MIXED16)
         return HEPT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;

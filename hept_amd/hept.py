@@ -19,7 +19,10 @@ MFMAs accurate to f32 round-off / "fp32_mfma" the same on the native f32 MFMA, s
 "fp32_diff" = "fp32_mfma" with the coordinate part of the logit as explicit differences: the mode for a trained
 ``w_rpe`` on un-normalised coordinates, where the reference's own fp32 logits are rounding noise; it trains in the
 same form (difference-form forward and backward, f32 tiles), so the forward is the same with and without grad /
-"bf16" MFMA tiles / "mixed16" = fp16 q̂,k̂ tiles with bf16 weights and values) and ``process_group`` (shard the ``n_hashes`` tables over
+"bf16" MFMA tiles / "mixed16" = fp16 q̂,k̂ tiles with bf16 weights and values / "mixed16_diff" = "mixed16" rows and
+matrix products for the feature columns with the coordinate part of the logit in f32 as explicit differences of
+``sqrt_w * coords``: the fast mode that stays right for a trained ``w_rpe`` on un-normalised coordinates; it trains as
+"fp32_diff" does and is not table-sharded) and ``process_group`` (shard the ``n_hashes`` tables over
 the ranks of a ``torch.distributed`` group).
 
 Inference (``torch.no_grad()``) runs the whole operator in one C call.  When gradients are
@@ -83,6 +86,9 @@ class HEPTAttention(nn.Module):
                 f"block_size={self.block_size}, n_hashes={self.n_hashes}")
         self.precision = precision
         ops.precision_code(precision)  # validate early
+        if precision == "mixed16_diff" and process_group is not None:
+            raise ValueError("precision='mixed16_diff' is not table-sharded (its block attention has no exchange path): "
+                             "construct without process_group, or use 'mixed16' / 'fp32_diff'")
         self.sharding: Optional[TableSharding] = (
             TableSharding(self.n_hashes, process_group) if process_group is not None else None
         )
@@ -252,11 +258,12 @@ class HEPTAttention(nn.Module):
     def _train_tiles(self) -> str:
         if self.train_tiles not in ("fp32", "bf16"):
             raise ValueError("train_tiles must be 'fp32' or 'bf16'")
-        return "fp32" if self.precision in ("fp32_mfma", "fp32_diff") else self.train_tiles
+        return "fp32" if self.precision in ("fp32_mfma", "fp32_diff", "mixed16_diff") else self.train_tiles
 
     def _train_f32_mfma(self):
-        """The ``f32_mfma`` argument of the training kernels, forward and backward: "diff" for ``precision="fp32_diff"``"""
-        return "diff" if self.precision == "fp32_diff" else self.precision == "fp32_mfma"
+        """The ``f32_mfma`` argument of the training kernels, forward and backward: "diff" for ``precision="fp32_diff"`` and
+        for "mixed16_diff", which takes the f32 form that matches its logit"""
+        return "diff" if self.precision in ("fp32_diff", "mixed16_diff") else self.precision == "fp32_mfma"
 
     def _train_fused_ok(self, x, kwargs) -> bool:
         """Whether the training-mode ``Attn`` block may hand its LayerNorm and projections to the fused row builder"""

@@ -13,10 +13,10 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import PREC_BF16, PREC_F32, PREC_F32_DIFF, PREC_F32_MFMA, PREC_MIXED16
+from ._lib import PREC_BF16, PREC_F32, PREC_F32_DIFF, PREC_F32_MFMA, PREC_MIXED16, PREC_MIXED16_DIFF
 
 __all__ = [
-    "precision_code", "rpe_scale", "prep_hash", "sort_tables", "block_attn", "reduce_tables", "combine_out",
+    "precision_code", "rpe_scale", "prep_hash", "sort_tables", "block_attn", "block_attn_coords", "reduce_tables", "combine_out",
     "forward", "forward_partial", "workspace_bytes", "profile_enable", "profile_read", "unpack_part",
     "segmented_argsort", "block_attn_bwd", "sort_tables_src", "forward_src", "forward_partial_src", "geo_args",
     "packed_partials", "prep_hash_fused", "combine_ffn", "attn_block_forward", "attn_block_forward_src", "attn_stack_forward",
@@ -27,10 +27,12 @@ __all__ = [
 
 
 def precision_code(precision) -> int:
-    if isinstance(precision, int) and not isinstance(precision, bool) and precision in (PREC_F32, PREC_BF16, PREC_MIXED16, PREC_F32_MFMA, PREC_F32_DIFF):
+    if isinstance(precision, int) and not isinstance(precision, bool) and precision in (PREC_F32, PREC_BF16, PREC_MIXED16, PREC_F32_MFMA, PREC_F32_DIFF, PREC_MIXED16_DIFF):
         return precision
     if precision == "mixed16":
         return PREC_MIXED16
+    if precision == "mixed16_diff":
+        return PREC_MIXED16_DIFF
     if precision in ("fp32", "f32") or precision is torch.float32:
         return PREC_F32
     if precision == "fp32_mfma":
@@ -39,7 +41,7 @@ def precision_code(precision) -> int:
         return PREC_F32_DIFF
     if precision == "bf16" or precision is torch.bfloat16:
         return PREC_BF16
-    raise ValueError(f"precision must be 'fp32', 'bf16', 'mixed16', 'fp32_mfma' or 'fp32_diff', got {precision!r}")
+    raise ValueError(f"precision must be 'fp32', 'bf16', 'mixed16', 'fp32_mfma', 'fp32_diff' or 'mixed16_diff', got {precision!r}")
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -194,7 +196,7 @@ def _raw_size(raw_size, n: int) -> int:
 
 # dtype tag of the row buffers: bf16 / f16 (mixed16: q^,k^ halves are fp16, the v half of kvhat is bf16) / f32
 _TILE = {PREC_F32: torch.float32, PREC_BF16: torch.bfloat16, PREC_MIXED16: torch.float16,
-         PREC_F32_MFMA: torch.float32, PREC_F32_DIFF: torch.float32}
+         PREC_F32_MFMA: torch.float32, PREC_F32_DIFF: torch.float32, PREC_MIXED16_DIFF: torch.float16}
 
 
 def _row_buffers(rows, prec: int, h: int, n: int, tl: int, dev) -> Dict[str, torch.Tensor]:
@@ -329,11 +331,12 @@ def segmented_argsort(keys: torch.Tensor, lens: Optional[torch.Tensor] = None) -
 
 
 @_on_device
-def block_attn(qhat, kvhat, qpos, kpos, head_dim: int, block_size: int, f32_mfma: bool = False) -> torch.Tensor:
+def block_attn(qhat, kvhat, qpos, kpos, head_dim: int, block_size: int, f32_mfma: bool = False, coords=None) -> torch.Tensor:
     """Per-table partial rows (Tl, N, H, row).  fp32 tiles: row = 32 f32 (numer in [:D], denom (+1e-20) at [D]);
     bf16 tiles with D == 24: packed row = 16 int32 dwords (24 bf16 numer | f32 denom | 0); see ``unpack_part``.
     ``f32_mfma`` runs f32 tiles on the native f32 MFMA instead of the split-bf16 products; ``f32_mfma="diff"`` the
-    difference form of the coordinate columns on top of that (``precision="fp32_diff"``)."""
+    difference form of the coordinate columns on top of that (``precision="fp32_diff"``).  ``coords`` = (coords (N, C),
+    sqrt_w (H, C), raw_size) on float16 rows: ``precision="mixed16_diff"`` (:func:`block_attn_coords`)."""
     lib = _lib.load()
     qhat, kvhat = _rowsc(qhat, "qhat"), _rowsc(kvhat, "kvhat")
     h, n, _ = qhat.shape
@@ -341,14 +344,41 @@ def block_attn(qhat, kvhat, qpos, kpos, head_dim: int, block_size: int, f32_mfma
     prec = {torch.float32: PREC_F32, torch.bfloat16: PREC_BF16, torch.float16: PREC_MIXED16}[qhat.dtype]
     if f32_mfma and prec == PREC_F32:
         prec = PREC_F32_DIFF if f32_mfma == "diff" else PREC_F32_MFMA
+    if coords is not None:
+        if prec != PREC_MIXED16:
+            raise TypeError("block_attn_coords takes the rows of precision 'mixed16' / 'mixed16_diff' (float16 row buffers)")
+        prec = PREC_MIXED16_DIFF
+        cds, sqrt_w, raw_size = coords
+        cds, sqrt_w = _f32c(cds, "coords"), _f32c(sqrt_w, "sqrt_w")
+        c = cds.shape[1]
+        # the kernel indexes these by the sizes above: a mismatch would be an out-of-bounds device read
+        if tuple(cds.shape) != (n, c) or tuple(sqrt_w.shape) != (h, c) or tuple(kvhat.shape) != (h, n, 64):
+            raise ValueError(f"coords must be ({n}, C) and sqrt_w ({h}, C), got {tuple(cds.shape)} and {tuple(sqrt_w.shape)}")
+        if tuple(qpos.shape) != (tl, h, n) or tuple(kpos.shape) != (tl, h, n):
+            raise ValueError(f"qpos and kpos must be ({tl}, {h}, {n})")
+        raw_size = n if raw_size is None else _raw_size(raw_size, n)
     packed = lib.hept_part_precision(prec, head_dim) == PREC_BF16
     qpos = qpos.to(torch.int32).contiguous()
     kpos = kpos.to(torch.int32).contiguous()
     part = torch.empty(tl, n, h, 16 if packed else 32, device=qhat.device, dtype=torch.int32 if packed else torch.float32)
+    if coords is not None:
+        _lib.check(lib.hept_block_attn_coords(qhat.data_ptr(), kvhat.data_ptr(), qpos.data_ptr(), kpos.data_ptr(),
+                                              cds.data_ptr(), sqrt_w.data_ptr(), raw_size, n, h, head_dim, c, tl,
+                                              block_size, part.data_ptr(), _stream(qhat)), "hept_block_attn_coords")
+        return part
     _lib.check(lib.hept_block_attn(qhat.data_ptr(), kvhat.data_ptr(), qpos.data_ptr(), kpos.data_ptr(), n, h,
                                    head_dim, tl, block_size, prec, part.data_ptr(), _stream(qhat)),
                "hept_block_attn")
     return part
+
+
+def block_attn_coords(qhat, kvhat, qpos, kpos, coords, sqrt_w, head_dim: int, block_size: int,
+                      raw_size: Optional[int] = None) -> torch.Tensor:
+    """``block_attn`` of ``precision="mixed16_diff"``: ``qhat`` / ``kvhat`` are "mixed16" rows (float16 tag) whose D feature
+    columns go through the matrix products, the coordinate part of every logit is formed in float32 from ``coords`` (N, C)
+    and ``sqrt_w`` (H, C) as explicit differences.  Rows at and after ``raw_size`` (src variant) count as coordinates 0.
+    Partial rows as ``block_attn`` writes them for "mixed16" (packed iff ``head_dim`` is 24)."""
+    return block_attn(qhat, kvhat, qpos, kpos, head_dim, block_size, coords=(coords, sqrt_w, raw_size))
 
 
 def _part_prec(part: torch.Tensor) -> int:

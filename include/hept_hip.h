@@ -65,6 +65,17 @@ extern "C" {
                                 w_rpe on un-normalised coordinates: terms of ~3e8 whose f32 sum is noise).  The mode for
                                 such inputs; mathematically the same operator (example/hept.py:8-12) */
 
+#define HEPT_PREC_MIXED16_DIFF 5 /* HEPT_PREC_MIXED16 rows and matrix products for the D feature columns, the coordinate part of
+                                    the logit in f32 as -1/2 sum_c (sqrt_w[h,c] cq_c - sqrt_w[h,c] ck_c)^2 from the caller's f32
+                                    coords: the 16-bit mode that stays right when sqrt_w . coords is large or leaves the
+                                    fp16 range (a trained w_rpe on raw coordinates).  Same rows, sort, partial rows and combine
+                                    as HEPT_PREC_MIXED16; the workspace adds an (H, C) f32 record for sqrt_w.  Run by
+                                    hept_forward*, hept_forward_src*, hept_attn_block_forward*, hept_attn_stack_forward* and
+                                    the staged hept_block_attn_coords; the table-sharded entries (hept_forward_partial*,
+                                    hept_partial_begin*, hept_partial_heads, hept_forward_sharded*) and hept_block_attn /
+                                    hept_block_attn_heads, which have no coordinates to give the kernel, answer
+                                    HEPT_ERR_SHAPE */
+
 /* Element type of q, k and v (one type for all three) at the *_in entry points.  Every bf16 and every fp16 value is an
  * f32 value: the row builder and the v-row riders widen the 16-bit rows in registers and run the same arithmetic, so
  * the results are bit-identical to the f32 entry points called on the widened tensors. */
@@ -141,6 +152,15 @@ int hept_block_attn(const void* qhat, const void* kvhat, const int32_t* qpos, co
 int hept_block_attn_heads(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,
                           int N, int H, int D, int Tl, int B, int precision, int h0, int hg, int hout, int hsub,
                           int n_rows_out, float* part, void* stream);
+
+/* hept_block_attn for HEPT_PREC_MIXED16_DIFF: qhat / kvhat are HEPT_PREC_MIXED16 rows (hept_prep_hash with either code),
+ * coords (N, C) f32 the caller's coordinates, sqrt_w (H, C) f32 the result of hept_rpe_scale; rows at and after raw_size
+ * (src variant; N otherwise) count as coordinates 0; as queries they keep the logit HEPT_PREC_MIXED16 forms for them (the
+ * key's stored norm), so the padding rows of both modes are bit-identical.  2 <= C, D + C <= 30, 0 <= raw_size <= N: HEPT_ERR_SHAPE otherwise.
+ * part: as hept_block_attn writes it for HEPT_PREC_MIXED16 (packed rows iff D == 24). */
+int hept_block_attn_coords(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,
+                           const float* coords, const float* sqrt_w, int raw_size, int N, int H, int D, int C, int Tl,
+                           int B, float* part, void* stream);
 
 /* Format of the partial rows hept_block_attn writes for (precision, D): HEPT_PREC_BF16 (packed) or
  * HEPT_PREC_F32. */
