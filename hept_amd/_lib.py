@@ -79,6 +79,7 @@ SIGNATURES = {
     "hept_block_attn_bwd_f32mfma": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),
     "hept_block_attn_bwd_diff": (c_int, [_P] * 5 + [c_int] * 6 + [_P] * 3),
     "hept_block_attn_bwd_bf16": (c_int, [_P] * 5 + [c_int] * 5 + [_P] * 3),
+    "hept_block_attn_bwd_coords": (c_int, [_P] * 7 + [c_int] * 7 + [_P] * 3),
     "hept_bwd_reduce": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_int] + [_P] * 6),
     "hept_bwd_reduce16": (c_int, [_P, _P] + [c_int] * 5 + [_P, c_int] + [_P] * 6),
     "hept_rpe_scale_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),

@@ -107,11 +107,26 @@ class RpeScale(torch.autograd.Function):
         return ops.rpe_scale_bwd(w, d_sqrt_w.contiguous(), h, d, k).to(w.dtype), None, None, None
 
 
+def _coords_tiles(tiles, f32_mfma, coords_dim=None, block_size=None) -> bool:
+    """Whether a node runs the 16-bit difference form (``tiles="mixed16"``: "mixed16" rows through ``ops.block_attn_coords``
+    and ``ops.block_attn_bwd_coords``); legal only together with ``f32_mfma="diff"``, the logit form it shares.  A shape
+    the backward kernel cannot hold (``ops.check_bwd_coords_shape``) is refused here, before the forward does any work."""
+    if tiles != "mixed16":
+        return False
+    if f32_mfma != "diff":
+        raise ValueError("tiles='mixed16' trains the difference form only: pass f32_mfma='diff' (precision 'mixed16_diff')")
+    if coords_dim is not None:
+        ops.check_bwd_coords_shape(coords_dim, block_size)
+    return True
+
+
 class HeptPartialSums(torch.autograd.Function):
     """(q, k, v, coords, sqrt_w) -> acc (N, H, 32) = sum over tables of [numer | denom | 0].
 
-    ``tiles``: "fp32" (the reference's arithmetic; split-bf16 products in both directions) or "bf16" (the rows and
-    kernels of the bf16 forward, one bf16 MFMA per product in the backward too -- ``HEPTAttention.train_tiles``).
+    ``tiles``: "fp32" (the reference's arithmetic; split-bf16 products in both directions), "bf16" (the rows and
+    kernels of the bf16 forward, one bf16 MFMA per product in the backward too -- ``HEPTAttention.train_tiles``) or
+    "mixed16" (with ``f32_mfma="diff"`` only: the rows and the block attention of ``precision="mixed16_diff"``, whose
+    backward ``ops.block_attn_bwd_coords`` recomputes that forward's logits and sums the coordinate gradient as differences).
 
     ``f32_mfma``: handed unchanged to ``ops.block_attn`` and ``ops.block_attn_bwd`` -- False (split-bf16 products), True
     (native f32 MFMA) or "diff" (``precision="fp32_diff"``: the difference form in both directions, so that the node's
@@ -127,6 +142,7 @@ class HeptPartialSums(torch.autograd.Function):
         n, hd = q.shape
         h = alpha.shape[0]
         d = hd // h
+        coords16 = _coords_tiles(tiles, f32_mfma, coords.shape[1], block_size)
         # hashes and the sort walk the tables in chunks of HEPT_MAX_TABLES, as the inference entry points do (the
         # reference takes any n_hashes, example/hept.py:37-41); the rows are rewritten identically by every chunk
         from ._lib import MAX_TABLES
@@ -147,12 +163,17 @@ class HeptPartialSums(torch.autograd.Function):
             qs.append(qp)
             ks.append(kp)
         qpos, kpos = (qs[0], ks[0]) if len(qs) == 1 else (torch.cat(qs), torch.cat(ks))
-        part = ops.block_attn(ph["qhat"], ph["kvhat"], qpos, kpos, d, block_size, f32_mfma=f32_mfma)
+        raw = n if geo is None else int(geo[3])
+        if coords16:
+            part = ops.block_attn_coords(ph["qhat"], ph["kvhat"], qpos, kpos, coords, sqrt_w, d, block_size, raw)
+        else:
+            part = ops.block_attn(ph["qhat"], ph["kvhat"], qpos, kpos, d, block_size, f32_mfma=f32_mfma)
         acc = ops.reduce_tables(part, d)
         ctx.f32_mfma = f32_mfma
+        ctx.coords16 = coords16
         ctx.save_for_backward(ph["qhat"], ph["kvhat"], qpos, kpos, coords, sqrt_w)
         ctx.dims = (d, coords.shape[1], block_size)
-        ctx.raw_size = n if geo is None else int(geo[3])
+        ctx.raw_size = raw
         return acc
 
     @staticmethod
@@ -164,7 +185,10 @@ class HeptPartialSums(torch.autograd.Function):
         # reduction kernel (as a torch einsum it was a 48 x N GEMM that rocBLAS ran in 320 us, as a product + column
         # sum two kernels of 27 us); rows at and after raw_size (src variant padding) get zero gradients there too
         h = qhat.shape[0]
-        if h * c <= 64:
+        if ctx.coords16:   # (d sqrt_w for any number of (head, coordinate) columns: ops.block_attn_bwd_coords)
+            dq, dk, dv, dcs, dsw = ops.block_attn_bwd_coords(qhat, kvhat, qpos, kpos, gacc.contiguous(), coords, sqrt_w, d,
+                                                             block_size, raw_size=ctx.raw_size)
+        elif h * c <= 64:
             dq, dk, dv, dcs, dsw = ops.block_attn_bwd(qhat, kvhat, qpos, kpos, gacc.contiguous(), d, c, block_size,
                                                       f32_mfma=ctx.f32_mfma, coords=coords, raw_size=ctx.raw_size)
         else:  # more (head, coordinate) columns than the reduction kernel's 64 lanes: the column sum in torch
@@ -201,6 +225,7 @@ class HeptPartialSumsFused(torch.autograd.Function):
         n, d = x.shape
         n_tables = alpha.shape[2]
         raw = n if geo is None else int(geo[3])
+        coords16 = _coords_tiles(tiles, f32_mfma, coords.shape[1], block_size)
         qs, ks = [], []
         rows = None   # see HeptPartialSums.forward
         for c0 in range(0, n_tables, MAX_TABLES):
@@ -215,9 +240,13 @@ class HeptPartialSumsFused(torch.autograd.Function):
             qs.append(qp)
             ks.append(kp)
         qpos, kpos = (qs[0], ks[0]) if len(qs) == 1 else (torch.cat(qs), torch.cat(ks))
-        part = ops.block_attn(ph["qhat"], ph["kvhat"], qpos, kpos, d, block_size, f32_mfma=f32_mfma)
+        if coords16:
+            part = ops.block_attn_coords(ph["qhat"], ph["kvhat"], qpos, kpos, coords, sqrt_w, d, block_size, raw)
+        else:
+            part = ops.block_attn(ph["qhat"], ph["kvhat"], qpos, kpos, d, block_size, f32_mfma=f32_mfma)
         acc = ops.reduce_tables(part, d)
         ctx.f32_mfma = f32_mfma
+        ctx.coords16 = coords16
         ctx.save_for_backward(ph["qhat"], ph["kvhat"], qpos, kpos, coords, sqrt_w, x, ln_w, ln_b, w_q, w_k, w_v)
         ctx.dims = (d, coords.shape[1], block_size, float(eps))
         ctx.raw_size = raw
@@ -228,8 +257,12 @@ class HeptPartialSumsFused(torch.autograd.Function):
     def backward(ctx, gacc):
         qhat, kvhat, qpos, kpos, coords, sqrt_w, x, ln_w, ln_b, w_q, w_k, w_v = ctx.saved_tensors
         d, c, block_size, eps = ctx.dims
-        dq, dk, dv, dcs, dsw = ops.block_attn_bwd(qhat, kvhat, qpos, kpos, gacc.contiguous(), d, c, block_size,
-                                                  f32_mfma=ctx.f32_mfma, coords=coords, raw_size=ctx.raw_size)
+        if ctx.coords16:
+            dq, dk, dv, dcs, dsw = ops.block_attn_bwd_coords(qhat, kvhat, qpos, kpos, gacc.contiguous(), coords, sqrt_w, d,
+                                                             block_size, raw_size=ctx.raw_size)
+        else:
+            dq, dk, dv, dcs, dsw = ops.block_attn_bwd(qhat, kvhat, qpos, kpos, gacc.contiguous(), d, c, block_size,
+                                                      f32_mfma=ctx.f32_mfma, coords=coords, raw_size=ctx.raw_size)
         need = ctx.needs_input_grad
         dx = dlw = dlb = dwq = dwk = dwv = None
         if any(need[i] for i in (0, 1, 2, 4, 5, 6)):   # (a frozen front end: nothing behind dq, dk, dv is computed)

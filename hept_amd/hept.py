@@ -22,7 +22,9 @@ same form (difference-form forward and backward, f32 tiles), so the forward is t
 "bf16" MFMA tiles / "mixed16" = fp16 q̂,k̂ tiles with bf16 weights and values / "mixed16_diff" = "mixed16" rows and
 matrix products for the feature columns with the coordinate part of the logit in f32 as explicit differences of
 ``sqrt_w * coords``: the fast mode that stays right for a trained ``w_rpe`` on un-normalised coordinates; it trains as
-"fp32_diff" does and is not table-sharded) and ``process_group`` (shard the ``n_hashes`` tables over
+"fp32_diff" does -- or, with ``train_tiles = "mixed16"`` (opt-in, this precision only), on its own 16-bit rows: the training
+forward is then the inference kernel and the backward its 16-bit difference form, 1.20 ms per training step at
+tracking-60k against 2.69 ms (``profiles/train_mixed16_diff16.txt``) -- and is not table-sharded) and ``process_group`` (shard the ``n_hashes`` tables over
 the ranks of a ``torch.distributed`` group).
 
 Inference (``torch.no_grad()``) runs the whole operator in one C call.  When gradients are
@@ -253,11 +255,19 @@ class HEPTAttention(nn.Module):
     # Tiles of the TRAINING path: "fp32" (default: the reference's arithmetic, gradients pinned on its autograd) or
     # "bf16" (opt-in: the bf16 forward's rows and one bf16 MFMA per product in the backward as well -- about half the
     # step time, gradients to the accuracy of a bf16 forward).  Set on the instance or the class.
+    # "mixed16" (opt-in, precision="mixed16_diff" only): that precision's own rows and block attention in the training
+    # forward, and the 16-bit difference-form backward (csrc/block_attn_bwd_coords.hip) -- the training forward is then the
+    # kernel the inference path runs.
     train_tiles = "fp32"
 
     def _train_tiles(self) -> str:
-        if self.train_tiles not in ("fp32", "bf16"):
-            raise ValueError("train_tiles must be 'fp32' or 'bf16'")
+        if self.train_tiles not in ("fp32", "bf16", "mixed16"):
+            raise ValueError("train_tiles must be 'fp32', 'bf16' or 'mixed16'")
+        if self.train_tiles == "mixed16":
+            if self.precision != "mixed16_diff":
+                raise ValueError(f"train_tiles='mixed16' needs precision='mixed16_diff' (it trains that mode's own rows); "
+                                 f"this module has precision={self.precision!r}")
+            return "mixed16"
         return "fp32" if self.precision in ("fp32_mfma", "fp32_diff", "mixed16_diff") else self.train_tiles
 
     def _train_f32_mfma(self):

@@ -18,7 +18,7 @@ from ._lib import PREC_BF16, PREC_F32, PREC_F32_DIFF, PREC_F32_MFMA, PREC_MIXED1
 __all__ = [
     "precision_code", "rpe_scale", "prep_hash", "sort_tables", "block_attn", "block_attn_coords", "reduce_tables", "combine_out",
     "forward", "forward_partial", "workspace_bytes", "profile_enable", "profile_read", "unpack_part",
-    "segmented_argsort", "block_attn_bwd", "sort_tables_src", "forward_src", "forward_partial_src", "geo_args",
+    "segmented_argsort", "block_attn_bwd", "block_attn_bwd_coords", "sort_tables_src", "forward_src", "forward_partial_src", "geo_args",
     "packed_partials", "prep_hash_fused", "combine_ffn", "attn_block_forward", "attn_block_forward_src", "attn_stack_forward",
     "attn_stack_forward_src", "combine_bwd", "rpe_scale_bwd",
     "partial_begin", "partial_heads", "combine_groups", "forward_sharded", "rows_wgrad", "ln_bwd", "ln_ffn_fwd",
@@ -478,6 +478,89 @@ def block_attn_bwd(qhat, kvhat, qpos, kpos, gacc, head_dim: int, coords_dim: int
     if coords is not None:
         return dq, dk, dv, dcs, dsw
     return dq, dk, dv, dcs
+
+
+def check_bwd_coords_shape(coords_dim: int, block_size: int) -> None:
+    """``block_attn_bwd_coords`` keeps five 16-bit tiles and three f32 side arrays of the coordinates in LDS (csrc/
+    block_attn_bwd_coords.hip: bwdc_lds): the widest rows on the largest blocks (coords_dim >= 26 with block_size > 224)
+    need more than the 160 KB of a CU.  Raises ``ValueError`` for such a shape -- the training path asks before its forward
+    runs, so that the refusal does not come out of ``loss.backward()``."""
+    nkt = (int(block_size) + 31) // 32
+    cs = {2: 2, 4: 4, 6: 8}.get(int(coords_dim), int(coords_dim))
+    need = 5 * 32 * nkt * 64 + 32 * nkt * 20 + 3 * 32 * nkt * cs * 4
+    if need > 160 * 1024:
+        raise ValueError(f"train_tiles='mixed16': coords_dim={coords_dim} with block_size={block_size} needs {need} bytes of "
+                         f"LDS in the backward (a CU has {160 * 1024}); train this shape with train_tiles='fp32'")
+
+
+def block_attn_bwd_coords(qhat, kvhat, qpos, kpos, gacc, coords, sqrt_w, head_dim: int, block_size: int,
+                          raw_size: Optional[int] = None):
+    """Backward of ``block_attn_coords`` + ``reduce_tables`` on the "mixed16" rows that forward gathers (float16 tag): gradient
+    rows gacc (N, H, 32) -> (dq, dk, dv (N, H*D), dcs (N, H, C), d_sqrt_w (H, C)).  The logits are recomputed as the forward
+    forms them (feature columns on the fp16 MFMA, the coordinate part in float32 as differences of ``sqrt_w * coords``), the
+    coordinate columns of the gradient are summed as differences; rows at and after ``raw_size`` get zeros.  With more than
+    64 (head, coordinate) columns d_sqrt_w is the column sum of ``dcs * coords`` in torch, as in the other training paths.
+    Every shape is checked before anything is loaded or launched: a mismatch would be an out-of-bounds device read."""
+    for name, t in (("qhat", qhat), ("kvhat", kvhat)):
+        if not torch.is_tensor(t) or t.dtype is not torch.float16:
+            raise TypeError(f"block_attn_bwd_coords takes the rows of precision 'mixed16' / 'mixed16_diff' (float16 row "
+                            f"buffers); {name} is {getattr(t, 'dtype', type(t).__name__)}")
+    for name, t in (("gacc", gacc), ("coords", coords), ("sqrt_w", sqrt_w)):
+        if not torch.is_tensor(t) or t.dtype is not torch.float32:
+            raise TypeError(f"{name} must be float32, got {getattr(t, 'dtype', type(t).__name__)}")
+    for name, t in (("qpos", qpos), ("kpos", kpos)):
+        if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be an int32 (or int64) tensor of positions, got {getattr(t, 'dtype', type(t).__name__)}")
+    if qhat.dim() != 3 or qhat.shape[2] != 32:
+        raise ValueError(f"qhat must be (H, N, 32), got {tuple(qhat.shape)}")
+    h, n, _ = qhat.shape
+    if tuple(kvhat.shape) != (h, n, 64):
+        raise ValueError(f"kvhat must be ({h}, {n}, 64), got {tuple(kvhat.shape)}")
+    if coords.dim() != 2 or coords.shape[0] != n:
+        raise ValueError(f"coords must be ({n}, C), got {tuple(coords.shape)}")
+    c = coords.shape[1]
+    if tuple(sqrt_w.shape) != (h, c):
+        raise ValueError(f"sqrt_w must be ({h}, {c}), got {tuple(sqrt_w.shape)}")
+    if qpos.dim() != 3 or tuple(qpos.shape[1:]) != (h, n) or tuple(kpos.shape) != tuple(qpos.shape):
+        raise ValueError(f"qpos and kpos must be (Tl, {h}, {n}), got {tuple(qpos.shape)} and {tuple(kpos.shape)}")
+    if tuple(gacc.shape) != (n, h, 32):
+        raise ValueError(f"gacc must be ({n}, {h}, 32), got {tuple(gacc.shape)}")
+    raw_size = n if raw_size is None else _raw_size(raw_size, n)
+    check_bwd_coords_shape(c, block_size)
+    return _block_attn_bwd_coords(qhat, kvhat, qpos, kpos, gacc, coords, sqrt_w, int(head_dim), int(block_size), raw_size)
+
+
+@_on_device
+def _block_attn_bwd_coords(qhat, kvhat, qpos, kpos, gacc, coords, sqrt_w, d, block_size, raw_size):
+    lib = _lib.load()
+    qhat, kvhat = _rowsc(qhat, "qhat"), _rowsc(kvhat, "kvhat")
+    gacc, coords, sqrt_w = _f32c(gacc, "grad of the partial sums"), _f32c(coords, "coords"), _f32c(sqrt_w, "sqrt_w")
+    h, n, _ = qhat.shape
+    tl, c = qpos.shape[0], coords.shape[1]
+    _lib.check(_check_shape_cached(n, h, d, c, tl, block_size), "hept_check_shape")
+    qpos = qpos.to(torch.int32).contiguous()
+    kpos = kpos.to(torch.int32).contiguous()
+    dev = qhat.device
+    # (zero-filled, not empty: the kernels write every element, but the allocation-site audit of the test suite admits
+    #  uninitialised buffers only at the sites its sweep drives; the fill of the per-table rows is part of the step time)
+    dq_part = torch.zeros(tl, n, h, 32, device=dev, dtype=torch.bfloat16)
+    dkv_part = torch.zeros(tl, n, h, 64, device=dev, dtype=torch.bfloat16)
+    st = _stream(qhat)
+    _lib.check(lib.hept_block_attn_bwd_coords(qhat.data_ptr(), kvhat.data_ptr(), qpos.data_ptr(), kpos.data_ptr(),
+                                              gacc.data_ptr(), coords.data_ptr(), sqrt_w.data_ptr(), raw_size, n, h, d, c,
+                                              tl, block_size, dq_part.data_ptr(), dkv_part.data_ptr(), st),
+               "hept_block_attn_bwd_coords")
+    dq = torch.zeros(n, h * d, device=dev, dtype=torch.float32)
+    dk, dv = torch.zeros_like(dq), torch.zeros_like(dq)
+    dcs = torch.zeros(n, h, c, device=dev, dtype=torch.float32)
+    in_kernel = h * c <= 64   # the reduction's d sqrt_w pass has 64 lanes
+    dsw = torch.zeros(h, c, device=dev, dtype=torch.float32) if in_kernel else None
+    _lib.check(lib.hept_bwd_reduce16(dq_part.data_ptr(), dkv_part.data_ptr(), tl, n, h, d, c,
+                                     coords.data_ptr() if in_kernel else None, raw_size, dq.data_ptr(), dk.data_ptr(),
+                                     dv.data_ptr(), dcs.data_ptr(), _ptr(dsw), st), "hept_bwd_reduce16")
+    if not in_kernel:
+        dsw = (dcs * coords[:, None, :]).sum(dim=0)
+    return dq, dk, dv, dcs, dsw
 
 
 @_on_device

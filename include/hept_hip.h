@@ -498,6 +498,18 @@ int hept_block_attn_bwd_diff(const float* qhat, const float* kvhat, const int32_
 int hept_block_attn_bwd_bf16(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,
                              const float* gacc, int N, int H, int D, int Tl, int B, void* dq_part16,
                              void* dkv_part16, void* stream);
+/* the backward of hept_block_attn_coords (HEPT_PREC_MIXED16_DIFF) on the rows that forward gathers: qhat / kvhat are
+ * HEPT_PREC_MIXED16 rows, coords (N, C) and sqrt_w (H, C) f32 as that entry takes them, rows at and after raw_size count as
+ * coordinates 0 and, as queries, keep the logit of the key's stored norm.  The logits are recomputed as the forward forms
+ * them (fp16 MFMA on the feature columns, the coordinate part in f32 as differences); dP and dV run on the bf16 MFMA as in
+ * hept_block_attn_bwd_bf16, with G in two bf16 pieces in dP; the stored fp16 q^ / k^ enter dS . K^ and dS^T . Q^ split exactly into two bf16 pieces; the
+ * coordinate columns of d q^ / d k^ are summed as sum_j dS_ij (sqrt_w ck_c[j] - sqrt_w cq_c[i]) in f32.  Same bf16
+ * dq_part16 / dkv_part16 rows as hept_block_attn_bwd_bf16, summed by hept_bwd_reduce16.  Null pointer: HEPT_ERR_ARG;
+ * hept_check_shape, raw_size outside [0, N], or C >= 26 with B > 224 (more LDS than a CU has): HEPT_ERR_SHAPE.  C = 2, 4, 6
+ * are specialised, any other C runs one launch that walks the coordinate columns two at a time. */
+int hept_block_attn_bwd_coords(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,
+                               const float* gacc, const float* coords, const float* sqrt_w, int raw_size, int N, int H,
+                               int D, int C, int Tl, int B, void* dq_part16, void* dkv_part16, void* stream);
 int hept_bwd_reduce16(const void* dq_part16, const void* dkv_part16, int Tl, int N, int H, int D, int C,
                       const float* coords, int raw_size, float* dq, float* dk, float* dv, float* dcs,
                       float* d_sqrt_w, void* stream);

@@ -2,7 +2,11 @@
 the opt-in bf16 tiles (``train_tiles = "bf16"``), and how far the bf16 gradients are from the fp32 ones.
 
 ``--precisions fp32,fp32_mfma,fp32_diff [--rounds 3]``: instead, the step time of each module precision (f32 training
-tiles), the precisions alternating in one process for the given number of rounds; prints every round and the median."""
+tiles), the precisions alternating in one process for the given number of rounds; prints every round and the median.
+
+``--modes mixed16_diff:fp32,mixed16_diff:mixed16,bf16:bf16 [--rounds 3]``: the same for (precision, train_tiles) pairs --
+the way to time ``train_tiles = "mixed16"`` (the 16-bit difference-form step of "mixed16_diff") against that precision's
+default f32 step and against the bf16-tiles step of a bf16 module, in one session."""
 import os
 import sys
 import time
@@ -63,6 +67,20 @@ if "--precisions" in sys.argv:
     for p in precisions:
         print(f"train step (fwd+bwd, precision {p}): median {sorted(times[p])[len(times[p]) // 2]:.3f} ms, "
               f"min {min(times[p]):.3f}, max {max(times[p]):.3f} over {rounds} rounds")
+    sys.exit(0)
+
+if "--modes" in sys.argv:
+    modes = [tuple(x.split(":")) for x in sys.argv[sys.argv.index("--modes") + 1].split(",")]
+    rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 3
+    times = {md: [] for md in modes}
+    for r in range(rounds):
+        for md in modes:
+            m.precision, m.train_tiles = md
+            times[md].append(timed())
+            print(f"round {r} train step (fwd+bwd, precision {md[0]}, train_tiles {md[1]}): {times[md][-1]:.3f} ms", flush=True)
+    for md in modes:
+        print(f"train step (fwd+bwd, precision {md[0]}, train_tiles {md[1]}): median {sorted(times[md])[len(times[md]) // 2]:.3f} ms, "
+              f"min {min(times[md]):.3f}, max {max(times[md]):.3f} over {rounds} rounds")
     sys.exit(0)
 
 ref_out, ref = None, None
