@@ -214,7 +214,7 @@ int run_begin(const Inputs& in, const Sizes& s, const Workspace& w, void* stream
     // K == 0: the caller passes sqrt_w itself (hept_rpe_scale)
     // The v half of the kvhat rows does not depend on anything this call computes: when the sort has a bucket-sort launch
     // (segments longer than the one-workgroup sort) that launch -- a latency-bound chain that leaves the memory system
-    // idle -- carries it as rider workgroups, and the row builder runs its q and k roles only (sort_tables.hip: RowsJob)
+    // idle -- carries it as rider workgroups, and the row builder runs its q and k roles only (rows_rider.h: RowsJob)
     const int raw_size = in.geo.eta ? in.geo.raw_size : s.N;
     // ... unless the launch is too short to hide them: with ONE local table (BASELINE config 4: one table per GPU) and
     // 16-bit rows the bucket sort is ~12 us of its own work against ~20 us of riders -- the row builder keeps its v

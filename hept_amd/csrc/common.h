@@ -304,11 +304,11 @@ int hept_sort_tables_src_rows(const float* qproj, const float* kproj, const floa
 void hept_sort_zero_block(void* sort_ws, int N, int H, int Tl, void** ptr, size_t* bytes);
 // stage timing (capi.hip, hept_profile_*): the sort calls this between its two launches
 void hept_prof_mark_sort_mid(void* stream);
-// hept_segmented_argsort for a caller that knows finite bounds of its keys (prepare.hip: packed code keys): the
-// per-segment range pass (a fill and a kernel) is skipped; any bounds give the exact stable sort
 // the launch behind HEPT_PREC_MIXED16_DIFF (block_attn_coords.hip); arguments checked by block_attn.hip's block_attn_impl
 int hept_block_attn_coords_launch(const void* qhat, const void* kvhat, const int32_t* qpos, const int32_t* kpos,
                                   const float* coords, const float* sqrt_w, int raw_size, int N, int H, int D, int C, int Tl,
                                   int B, const HeadRange& hr, float* part, void* stream);
+// hept_segmented_argsort for a caller that knows finite bounds of its keys (prepare.hip: packed code keys): the
+// per-segment range pass (a fill and a kernel) is skipped; any bounds give the exact stable sort
 int hept_segmented_argsort_bounded(const float* keys, int S, int L, float lo, float hi, void* ws, int32_t* pos,
                                    void* stream);

@@ -1,6 +1,6 @@
 // sort_tables: AND-shifted sort keys + exact stable segmented sort: one counting pass on the top bits of a monotone
 // bucket id, then every bucket is finished inside LDS.  Two kernels; the second one also carries the v rows of the row
-// builder as rider workgroups (RowsJob below).
+// builder as rider workgroups (rows_rider.h).
 //
 // Replaces, for tables [t0, t0+Tl) (reference file:line):
 //   hash_shift = max - min            example/hept_utils.py:70
@@ -31,6 +31,7 @@
 // neighbour rank 89 us -> keygen / scatter / bucket sort 40 us (three launches, 11.5 MB of keys and 23 MB of pairs
 // written and read back) -> this design (two launches, keys never leave the chip).
 #include "common.h"
+#include "rows_rider.h"
 
 namespace {
 
@@ -65,12 +66,91 @@ __device__ __forceinline__ unsigned int ordered_bits(float key) {
 __device__ __forceinline__ float from_ordered(unsigned int u) {
     return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
-// monotone HEPT_ID_BITS-bit bucket id; scale = 2^bits / (kmax - kmin), 0 when all keys are equal
+// monotone bucket id in [0, BUCKETS) (ID_BUCKETS: KA / KB; SMALL_BINS: the one-workgroup sort); scale = id_scale()
+template <int BUCKETS>
 __device__ __forceinline__ unsigned int bucket_id(unsigned int u, float kmin, float scale) {
     // the float clamp keeps +inf keys (the src variant's padding rows) and inf * 0 = NaN in the last bucket
-    const float x = fminf((from_ordered(u) - kmin) * scale, (float)(ID_BUCKETS - 1));
+    const float x = fminf((from_ordered(u) - kmin) * scale, (float)(BUCKETS - 1));
     const int b = (int)x;
     return (unsigned int)(b < 0 ? 0 : b);
+}
+// scale = buckets / (kmax - kmin), 0 when all keys are equal
+__device__ __forceinline__ float id_scale(float width, int buckets) {
+    float scale = width > 0.f ? (float)buckets / width : 0.f;
+    if (!(scale < 3.0e38f)) scale = 0.f;  // inf/nan guard for denormal widths: one bucket, still exact
+    return scale;
+}
+
+// ---- the key rule (KA, the one-workgroup sort) -----------------------------------------------------------------------
+// MODE 0: key = proj + float(code) * span as TWO rounded ops (the two eager ops of the reference, example/hept.py:63-65;
+// HIP's __fmul_rn / __fadd_rn are plain * and + and would be contracted to one fma without -ffp-contract=off (Makefile)
+// -- the asm barrier makes it explicit here as well);  MODE 1: the src variant's float shift (get_geo_shift,
+// src/models/attention/hept.py:46-56): shift = (phi * span) * cfac + eta * span, every operation rounded on its own;
+// MODE 2: raw keys, the key is the value itself.  One overload per mode that forms a key.
+__device__ __forceinline__ float sort_key(float proj, long long code, float span) {   // MODE 0
+    float off = (float)code * span;
+    asm volatile("" : "+v"(off));
+    return proj + off;
+}
+__device__ __forceinline__ float sort_key(float proj, float eta, float phi, float cf, float span) {   // MODE 1
+    float t1 = eta * span;
+    asm volatile("" : "+v"(t1));
+    float t2 = phi * span;
+    asm volatile("" : "+v"(t2));
+    t2 = t2 * cf;
+    asm volatile("" : "+v"(t2));
+    float t3 = t2 + t1;
+    asm volatile("" : "+v"(t3));
+    return proj + t3;
+}
+// src variant: bound of the shift in units of span, from m = max_n (phi * cfac + eta) over the finite rows
+__device__ __forceinline__ float src_shift_bound(float m) { return m * 1.0001f + 1.f; }   // slack for the roundings
+// (lo, hi, cmax) of a workgroup of WAVES waves from every thread's share; passes one barrier
+template <int WAVES>
+__device__ __forceinline__ void reduce_range(float& lo, float& hi, float& cmax, float (&red_s)[3][WAVES]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, off));
+        hi = fmaxf(hi, __shfl_xor(hi, off));
+        cmax = fmaxf(cmax, __shfl_xor(cmax, off));
+    }
+    if (lane == 0) { red_s[0][w] = lo; red_s[1][w] = hi; red_s[2][w] = cmax; }
+    __syncthreads();
+    lo = red_s[0][0]; hi = red_s[1][0]; cmax = red_s[2][0];
+#pragma unroll
+    for (int ww = 1; ww < WAVES; ++ww) {
+        lo = fminf(lo, red_s[0][ww]); hi = fmaxf(hi, red_s[1][ww]); cmax = fmaxf(cmax, red_s[2][ww]);
+    }
+}
+
+// Exclusive prefix over the bins of a workgroup of WAVES waves.  Every thread owns BPT consecutive bins, in thread order;
+// c[] holds its counts on entry and the bins' first positions on return.  Returns the sum of all bins.  Passes one
+// barrier; wsum_s: [WAVES].  (The digit prefix of KA is not a caller: its 256 digits belong to the first 4 of 8 waves,
+// which would put a test of the wave index here that no other caller needs.)
+template <int BPT, int WAVES>
+__device__ __forceinline__ unsigned int exclusive_prefix(unsigned int (&c)[BPT], unsigned int* __restrict__ wsum_s) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned int tot = 0;
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) tot += c[u];
+    const unsigned int incl = hept_wave_scan_add(tot);
+    if (lane == 63) wsum_s[w] = incl;
+    __syncthreads();
+    unsigned int run = incl - tot, all = 0;
+#pragma unroll
+    for (int ww = 0; ww < WAVES; ++ww) {
+        const unsigned int ws = wsum_s[ww];
+        run += ww < w ? ws : 0u;
+        all += ws;
+    }
+#pragma unroll
+    for (int u = 0; u < BPT; ++u) {
+        const unsigned int first = run;
+        run += c[u];
+        c[u] = first;
+    }
+    return all;
 }
 
 // per-segment id map parameters, written once by KA (chunk 0) and read by KB
@@ -118,15 +198,12 @@ static_assert(TOP_SHIFT + EMBED_SHIFT <= 32, "low id bits + index fit the low wo
 // per-thread item loops of that chain and double the waves that hide its latencies.
 //   loads of the chunk's hashes and codes (issued first: they do not depend on the key range)
 //   -> key range of the segment (the prep kernel's per-workgroup partials, 16 KiB from L2)
-//   -> keys: key = proj + float(code) * span as TWO rounded ops (the two eager ops of the reference,
-//      example/hept.py:63-65; HIP's __fmul_rn / __fadd_rn are plain * and + and would be contracted to one fma
-//      without -ffp-contract=off (Makefile) -- the asm barrier makes it explicit here as well)
+//   -> keys (sort_key)
 //   -> digit = top id bits; local slot = LDS atomic on the digit counter; exclusive prefix over the digits
 //   -> pairs into the LDS stage in digit order -> one linear, fully coalesced run of pairs[seg][chunk * 4096 ...]
 //      + tab[seg][chunk][0..256] = first position of every digit inside the run (tab[..][256] = pairs of the chunk)
-// MODE 0: example keys;  MODE 1: the src variant's float shift (get_geo_shift, src/models/attention/hept.py:46-56):
-// shift = (phi * span) * cfac + eta * span, every operation rounded on its own, key bound from the third partial column
-// (src_bound_kernel);  MODE 2: raw keys (hept_segmented_argsort), range from raw_range_kernel.
+// MODE 0: example keys;  MODE 1: the src variant, key bound from the third partial column (src_bound_kernel);
+// MODE 2: raw keys (hept_segmented_argsort), range from raw_range_kernel.
 #ifndef HEPT_SCATTER_THREADS
 #define HEPT_SCATTER_THREADS 512
 #endif
@@ -216,8 +293,7 @@ __global__ __launch_bounds__(SCT) void chunk_sort_kernel(
             lo = range_lo;
             hi = range_hi;
         }
-        const float width = hi - lo;
-        scale = width > 0.f ? (float)ID_BUCKETS / width : 0.f;
+        scale = id_scale(hi - lo, ID_BUCKETS);
     } else {
         // hash range + largest code of this (table, head): reduce the prep kernel's per-workgroup partials
         float hi = -INFINITY, cmax = 0.f;
@@ -232,25 +308,12 @@ __global__ __launch_bounds__(SCT) void chunk_sort_kernel(
             hi = fmaxf(hi, m[i][1]);
             cmax = fmaxf(cmax, m[i][2]);
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            lo = fminf(lo, __shfl_xor(lo, off));
-            hi = fmaxf(hi, __shfl_xor(hi, off));
-            cmax = fmaxf(cmax, __shfl_xor(cmax, off));
-        }
-        if (lane == 0) { red_s[0][w] = lo; red_s[1][w] = hi; red_s[2][w] = cmax; }
-        __syncthreads();
-        lo = red_s[0][0]; hi = red_s[1][0]; cmax = red_s[2][0];
-#pragma unroll
-        for (int ww = 1; ww < SCT_WAVES; ++ww) {
-            lo = fminf(lo, red_s[0][ww]); hi = fmaxf(hi, red_s[1][ww]); cmax = fmaxf(cmax, red_s[2][ww]);
-        }
+        reduce_range(lo, hi, cmax, red_s);
         span = hi - lo;
         // keys lie in [lo, hi + cmax*span] (codes >= 0); any key outside is clamped by bucket_id (still monotone)
         const float width = (hi + cmax * span) - lo;
-        scale = width > 0.f ? (float)ID_BUCKETS / width : 0.f;
+        scale = id_scale(width, ID_BUCKETS);
     }
-    if (!(scale < 3.0e38f)) scale = 0.f;  // inf/nan guard for denormal widths: one bucket, still exact
     if (chunk == 0 && tid == 0) seg_params[seg] = SegParams{lo, scale};
     if (MODE == 2) __syncthreads();   // (the other modes passed a barrier in the range reduction: cnt_s is zero)
 
@@ -263,26 +326,11 @@ __global__ __launch_bounds__(SCT) void chunk_sort_kernel(
 #pragma unroll
     for (int r = 0; r < SCT_ITEMS; ++r) {
         const int n = base + ((r >> 2) * SCT + tid) * 4 + (r & 3);
-        float kf;
-        if constexpr (MODE == 0) {
-            float off = (float)cd[r] * span;
-            asm volatile("" : "+v"(off));
-            kf = pj[r] + off;
-        } else if constexpr (MODE == 1) {
-            float t1 = ev[r] * span;
-            asm volatile("" : "+v"(t1));
-            float t2 = pv[r] * span;
-            asm volatile("" : "+v"(t2));
-            t2 = t2 * cf;
-            asm volatile("" : "+v"(t2));
-            float t3 = t2 + t1;
-            asm volatile("" : "+v"(t3));
-            kf = pj[r] + t3;
-        } else {
-            kf = pj[r];
-        }
+        float kf = pj[r];
+        if constexpr (MODE == 0) kf = sort_key(pj[r], cd[r], span);
+        if constexpr (MODE == 1) kf = sort_key(pj[r], ev[r], pv[r], cf, span);
         key[r] = ordered_bits(kf);
-        const unsigned int id = bucket_id(key[r], lo, scale);
+        const unsigned int id = bucket_id<ID_BUCKETS>(key[r], lo, scale);
         const unsigned int dg = id >> TOP_SHIFT;
         lowid[r] = (unsigned short)(id & (unsigned int)(LOBINS - 1));
         dig[r] = (unsigned char)dg;
@@ -297,15 +345,20 @@ __global__ __launch_bounds__(SCT) void chunk_sort_kernel(
     if constexpr (REGION) {
         if (digit && total) gbase = atomicAdd(rg.cnt + (size_t)seg * NTOP + tid, total);
     }
-    const unsigned int incl = hept_wave_scan_add(total);
-    if (digit && lane == 63) wsum_s[w] = incl;
-    __syncthreads();
-    const int n_valid = max(0, min(SORT_CHUNK, len - base));
-    unsigned int first = incl - total;
-    if (digit) {
+    // exclusive prefix over the digits (one per thread of the first RADIX / 64 waves); passes one barrier
+    auto digit_prefix = [&](unsigned int count) {
+        const unsigned int incl = hept_wave_scan_add(count);
+        if (digit && lane == 63) wsum_s[w] = incl;
+        __syncthreads();
+        unsigned int first = incl - count;
 #pragma unroll
         for (int ww = 0; ww < RADIX / HEPT_WAVE; ++ww)
             if (ww < w) first += wsum_s[ww];
+        return first;
+    };
+    const unsigned int first = digit_prefix(total);
+    const int n_valid = max(0, min(SORT_CHUNK, len - base));
+    if (digit) {
         start_s[tid] = first;
         if constexpr (!REGION) {
             unsigned int* my_tab = tab + ((size_t)seg * n_chunks + chunk) * TAB;
@@ -350,14 +403,8 @@ __global__ __launch_bounds__(SCT) void chunk_sort_kernel(
             // some run crosses the end of its region: those pairs go to the segment's overflow pool, packed by an
             // exclusive prefix over the digits' overflow counts behind one bump of the pool cursor
             const unsigned int ov = digit ? over_s[tid] : 0u;
-            const unsigned int oincl = hept_wave_scan_add(ov);
-            if (digit && lane == 63) wsum_s[w] = oincl;
-            __syncthreads();
+            const unsigned int ofirst = digit_prefix(ov);
             if (digit) {
-                unsigned int ofirst = oincl - ov;
-#pragma unroll
-                for (int ww = 0; ww < RADIX / HEPT_WAVE; ++ww)
-                    if (ww < w) ofirst += wsum_s[ww];
                 over_s[tid] = ofirst;
                 if (tid == RADIX - 1) over_s[RADIX + 1] = atomicAdd(rg.cnt + (size_t)rg.segs * NTOP + seg, ofirst + ov);
             }
@@ -414,179 +461,18 @@ __global__ __launch_bounds__(SCT) void chunk_sort_kernel(
 // CAP^2 compares.
 constexpr int BKT_THREADS = HEPT_BKT_THREADS;
 constexpr int BKT_WAVES = BKT_THREADS / HEPT_WAVE;
-
-// ---- riders: the v half of the kvhat rows, written by workgroups that travel in the KB launch -------------------------
-// KB is a chain of short dependent steps per workgroup: it moves 35 MB in 21 us and leaves the memory system idle most
-// of that time.  The v role of the row builder (prep_hash.hip: [v | 1.0 at column D | 0 ..] per (head, point)) is the
-// opposite -- a pure format conversion of 77 MB with no dependence on anything the forward computes -- so the first
-// `vy` rows of the KB grid do it instead of sorting: no LDS and no more registers than KB itself (the launch's
-// resources stay KB's).  Same values as the v role (the same bf16 conversion).  Measured at tracking-60k (bf16 / f32
-// tiles): row builder 55.2 -> 46.2 / 65.2 -> 53.2 us, sort 37.2 -> 44.3 / 38.0 -> 47.7 us, forward -2.3 us; the riders
-// alone take ~20 us (a rider wave is its own chain of load -> convert -> store trips), so more of them (8 grid rows:
-// +4 us) or fewer (2: +1 us) are both worse than 3, and the q / k roles that stay behind run at 3.9 TB/s instead of
-// the three roles' 4.7 -- the v role was already filling their gaps.
-struct RowsJob {
-    const void* v;      // (N, H * D) fp32, or bf16 / fp16 at an 8-byte aligned base (`in`)
-    char* kvhat;        // (H, N, 2 * qrow bytes): v half at byte qrow of a row
-    int N, raw_size;    // rows >= raw_size are padding: v = 0 (src variant)
-    int H, D4;          // D / 4
-    int f32;            // 1: f32 tile rows (qrow = 128 B), 0: 16-bit rows (qrow = 64 B)
-    int vy;             // grid rows (of gridDim.x workgroups each) that are riders; 0: none
-    int in;             // HEPT_IN_*: element type of v
-};
-#ifndef HEPT_ROWS_RIDERS
-#define HEPT_ROWS_RIDERS 3
-#endif
-// 16-bit v (IN = HEPT_IN_BF16 / HEPT_IN_F16): the same tiles, pieces and trips on half the input bytes.  A source address
-// is only 8-byte aligned in general (any D % 4 == 0), so the input moves as 8-byte loads of 4 elements: one per piece of
-// an f32 row, two per piece of a 16-bit row (half the load registers of the f32 input either way), widened at the store
-// (common.h: hept_widen4).  The 1.0 of column D travels as the input type's own 1.0 in the otherwise zero piece.  bf16
-// input into bf16 rows is a repack of the same bits (= hept_pack_bf16 of the widened values: bf16 -> f32 -> bf16 is
-// the identity).
-template <int H_, int IN>
-__device__ __forceinline__ void rows_rider16(const RowsJob& jb, unsigned int wg, unsigned int n_wgs) {
-    const unsigned int H = H_ ? H_ : (unsigned int)jb.H, D = 4u * (unsigned int)jb.D4, HD = H * D;
-    const unsigned int lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const unsigned int ntiles = ((unsigned int)jb.N + 7u) >> 3;
-    const unsigned int wave = wg * BKT_WAVES + wv, n_waves = n_wgs * BKT_WAVES;
-    const unsigned short* v16 = reinterpret_cast<const unsigned short*>(jb.v);
-    constexpr unsigned int ONE = IN == HEPT_IN_BF16 ? 0x3F80u : 0x3C00u;   // 1.0 in the low half of a dword
-    if (jb.f32) {
-        constexpr unsigned int PPR = 8, IT = 4;
-        for (unsigned int tile = wave; tile < ntiles; tile += n_waves) {
-            const unsigned int n0 = tile << 3;
-            for (unsigned int i0 = 0; i0 < H * 8 * PPR; i0 += 64 * IT) {
-                u32x2 x[IT];
-                unsigned int hd[IT], n[IT], k[IT];
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u) {
-                    const unsigned int i = i0 + u * 64 + lane;
-                    k[u] = i & (PPR - 1);
-                    n[u] = n0 + ((i / PPR) & 7u);
-                    hd[u] = i / (8 * PPR);
-                    const bool data = hd[u] < H && n[u] < (unsigned int)jb.raw_size && 4 * k[u] < D;
-                    x[u] = data ? hept_ld<HEPT_NT_RIDER_IN32>(reinterpret_cast<const u32x2*>(v16 + (size_t)n[u] * HD + hd[u] * D + 4 * k[u]))
-                                : u32x2{4 * k[u] == D ? ONE : 0u, 0u};
-                }
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u)
-                    if (hd[u] < H && n[u] < (unsigned int)jb.N)
-                        *reinterpret_cast<f32x4*>(jb.kvhat + ((size_t)hd[u] * jb.N + n[u]) * 256 + 128 + k[u] * 16) =
-                            hept_widen4<IN>(x[u][0], x[u][1]);
-            }
-        }
-    } else {
-        constexpr unsigned int PPR = 4, IT = 2;
-        for (unsigned int tile = wave; tile < ntiles; tile += n_waves) {
-            const unsigned int n0 = tile << 3;
-            for (unsigned int i0 = 0; i0 < H * 8 * PPR; i0 += 64 * IT) {
-                u32x2 x[IT][2];
-                unsigned int hd[IT], n[IT], k[IT];
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u) {
-                    const unsigned int i = i0 + u * 64 + lane;
-                    k[u] = i & (PPR - 1);
-                    n[u] = n0 + ((i / PPR) & 7u);
-                    hd[u] = i / (8 * PPR);
-                    const bool row = hd[u] < H && n[u] < (unsigned int)jb.raw_size;
-                    const unsigned short* src = v16 + (size_t)n[u] * HD + hd[u] * D + 8 * k[u];
-                    x[u][0] = (row && 8 * k[u] < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const u32x2*>(src)) : u32x2{0u, 0u};
-                    x[u][1] = (row && 8 * k[u] + 4 < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const u32x2*>(src + 4)) : u32x2{0u, 0u};
-                    // the 1.0 of column D (D % 4 == 0: the first element of one of the two quads, which is not loaded)
-                    if (8 * k[u] == D) x[u][0][0] = ONE;
-                    if (8 * k[u] + 4 == D) x[u][1][0] = ONE;
-                }
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u)
-                    if (hd[u] < H && n[u] < (unsigned int)jb.N) {
-                        u32x4 out = u32x4{x[u][0][0], x[u][0][1], x[u][1][0], x[u][1][1]};
-                        if constexpr (IN != HEPT_IN_BF16) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) out[j] = hept_pack_bf16(hept_in_lo<IN>(out[j]), hept_in_hi<IN>(out[j]));
-                        }
-                        *reinterpret_cast<u32x4*>(jb.kvhat + ((size_t)hd[u] * jb.N + n[u]) * 128 + 64 + k[u] * 16) = out;
-                    }
-            }
-        }
-    }
-}
-
-template <int H_>   // 0: run-time head count
-__device__ __forceinline__ void rows_rider(const RowsJob& jb, unsigned int wg, unsigned int n_wgs) {
-    if (jb.in == HEPT_IN_BF16) return rows_rider16<H_, HEPT_IN_BF16>(jb, wg, n_wgs);
-    if (jb.in == HEPT_IN_F16) return rows_rider16<H_, HEPT_IN_F16>(jb, wg, n_wgs);
-    const float* v32 = reinterpret_cast<const float*>(jb.v);
-    // A wave takes a tile of 8 consecutive points (one contiguous run of v) at a time.  A row half is PPR 16-B pieces
-    // (4 of 8 bf16 values, or 8 of 4 floats); lane order inside the tile is [head][point][piece]: a store instruction
-    // writes whole 64-B / 128-B row halves of consecutive points of one head -- the pattern of the row builder's
-    // copy-out -- and piece k of row (h, n) reads v[n][h*D + 8k ..] (bf16) or [.. + 4k ..] (f32): elements below D are
-    // data, element D is the 1.0 that makes P.V produce the denominator, the rest zeros.  All loads of a tile are in
-    // flight before the first conversion (trips of 2 / 4 instructions: the riders must not raise the launch's register
-    // count above KB's own); the 128-B lines of the run are shared by the wave's instructions through L1.
-    const unsigned int H = H_ ? H_ : (unsigned int)jb.H, D = 4u * (unsigned int)jb.D4, HD = H * D;
-    const unsigned int lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const unsigned int ntiles = ((unsigned int)jb.N + 7u) >> 3;
-    const unsigned int wave = wg * BKT_WAVES + wv, n_waves = n_wgs * BKT_WAVES;
-    if (jb.f32) {
-        constexpr unsigned int PPR = 8, IT = 4;   // pieces per row half; wave instructions per trip (16 at H = 8 per tile: 4 trips)
-        for (unsigned int tile = wave; tile < ntiles; tile += n_waves) {
-            const unsigned int n0 = tile << 3;
-            for (unsigned int i0 = 0; i0 < H * 8 * PPR; i0 += 64 * IT) {
-                f32x4 x[IT];
-                unsigned int hd[IT], n[IT], k[IT];
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u) {
-                    const unsigned int i = i0 + u * 64 + lane;
-                    k[u] = i & (PPR - 1);
-                    n[u] = n0 + ((i / PPR) & 7u);
-                    hd[u] = i / (8 * PPR);
-                    const bool data = hd[u] < H && n[u] < (unsigned int)jb.raw_size && 4 * k[u] < D;
-                    x[u] = data ? hept_ld<HEPT_NT_RIDER_IN32>(reinterpret_cast<const f32x4*>(v32 + (size_t)n[u] * HD + hd[u] * D + 4 * k[u]))
-                                : f32x4{4 * k[u] == D ? 1.f : 0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u)
-                    if (hd[u] < H && n[u] < (unsigned int)jb.N)
-                        *reinterpret_cast<f32x4*>(jb.kvhat + ((size_t)hd[u] * jb.N + n[u]) * 256 + 128 + k[u] * 16) = x[u];
-            }
-        }
-    } else {
-        constexpr unsigned int PPR = 4, IT = 2;   // (register budget: the launch's VGPR count must stay KB's)
-        for (unsigned int tile = wave; tile < ntiles; tile += n_waves) {
-            const unsigned int n0 = tile << 3;
-            for (unsigned int i0 = 0; i0 < H * 8 * PPR; i0 += 64 * IT) {
-                f32x4 x[IT][2];
-                unsigned int hd[IT], n[IT], k[IT];
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u) {
-                    const unsigned int i = i0 + u * 64 + lane;
-                    k[u] = i & (PPR - 1);
-                    n[u] = n0 + ((i / PPR) & 7u);
-                    hd[u] = i / (8 * PPR);
-                    const bool row = hd[u] < H && n[u] < (unsigned int)jb.raw_size;
-                    const float* src = v32 + (size_t)n[u] * HD + hd[u] * D + 8 * k[u];
-                    x[u][0] = (row && 8 * k[u] < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const f32x4*>(src)) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    x[u][1] = (row && 8 * k[u] + 4 < D) ? hept_ld<HEPT_NT_RIDER_IN16>(reinterpret_cast<const f32x4*>(src + 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    // the 1.0 of column D (D % 4 == 0: the first element of one of the two quads)
-                    if (8 * k[u] == D) x[u][0][0] = 1.f;
-                    if (8 * k[u] + 4 == D) x[u][1][0] = 1.f;
-                }
-#pragma unroll
-                for (unsigned int u = 0; u < IT; ++u)
-                    if (hd[u] < H && n[u] < (unsigned int)jb.N)
-                        *reinterpret_cast<u32x4*>(jb.kvhat + ((size_t)hd[u] * jb.N + n[u]) * 128 + 64 + k[u] * 16) =
-                            u32x4{hept_pack_bf16(x[u][0][0], x[u][0][1]), hept_pack_bf16(x[u][0][2], x[u][0][3]),
-                                  hept_pack_bf16(x[u][1][0], x[u][1][1]), hept_pack_bf16(x[u][1][2], x[u][1][3])};
-            }
-        }
-    }
-}
-
 constexpr int BKT_BINS_PER_THREAD = LOBINS / BKT_THREADS;
 static_assert(LOBINS % BKT_THREADS == 0, "every thread owns the same number of bins");
-// MAXR = chunks whose run offsets fit the kernel's LDS table (64: every wave builds the table by itself with one
-// shuffle scan, no barrier; the large-tile kernel takes up to 1024 chunks = 4 M keys per segment through a serial
-// scan); longer segments walk the global table for every lookup -- slow, never wrong
+static_assert(BKT_BINS_PER_THREAD == 4, "bins per thread: one 16-B LDS access");
+// histogram -> first positions, in place: thread owns bins 4 tid .. 4 tid + 3 (bin_s at a 16-B boundary)
+__device__ __forceinline__ void bucket_prefix_bins(unsigned int* __restrict__ bin_s, unsigned int* __restrict__ wsum_s) {
+    u32x4* mine = reinterpret_cast<u32x4*>(bin_s + 4 * threadIdx.x);
+    const u32x4 h = *mine;
+    unsigned int c[4] = {h[0], h[1], h[2], h[3]};
+    exclusive_prefix<4, BKT_WAVES>(c, wsum_s);
+    *mine = u32x4{c[0], c[1], c[2], c[3]};
+}
+
 // The common bucket of the REGION layout (nb <= LEAN_SLOTS * threads pairs, all of them in registers, low id bits embedded):
 // the same three steps as the general code below -- histogram of the low id bits, exclusive prefix, scatter into the
 // tile -- but every thread ranks ITS OWN pairs straight from its registers: the scatter's atomic told it the group, the
@@ -601,8 +487,7 @@ constexpr int LEAN_SLOTS = HEPT_LEAN_SLOTS;
 __device__ __forceinline__ void bucket_lean(const unsigned long long (&pr)[LEAN_SLOTS], int nb, int start,
                                             unsigned long long* __restrict__ tile_s, unsigned int* __restrict__ cur_s,
                                             unsigned int* __restrict__ wsum_s, int* __restrict__ out) {
-    static_assert(BKT_BINS_PER_THREAD == 4, "bins per thread: one 16-B LDS access");
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     unsigned int* bin_s = cur_s + 1;
     unsigned int d[LEAN_SLOTS];
 #pragma unroll
@@ -612,20 +497,7 @@ __device__ __forceinline__ void bucket_lean(const unsigned long long (&pr)[LEAN_
         if (u * BKT_THREADS + tid < nb) atomicAdd(&bin_s[d[u]], 1u);
     }
     __syncthreads();
-    {   // exclusive prefix over the bins: thread owns bins 4 tid .. 4 tid + 3
-        const u32x4 c = *reinterpret_cast<const u32x4*>(bin_s + 4 * tid);
-        const unsigned int tot = c[0] + c[1] + c[2] + c[3];
-        const unsigned int incl = hept_wave_scan_add(tot);
-        if (lane == 63) wsum_s[w] = incl;
-        __syncthreads();
-        unsigned int run = incl - tot;
-#pragma unroll
-        for (int ww = 0; ww < BKT_WAVES; ++ww)
-            if (ww < w) run += wsum_s[ww];
-        u32x4 e;
-        e[0] = run; e[1] = run + c[0]; e[2] = e[1] + c[1]; e[3] = e[2] + c[2];
-        *reinterpret_cast<u32x4*>(bin_s + 4 * tid) = e;
-    }
+    bucket_prefix_bins(bin_s, wsum_s);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < LEAN_SLOTS; ++u) {
@@ -652,29 +524,27 @@ __device__ __forceinline__ void bucket_lean(const unsigned long long (&pr)[LEAN_
 // loads depend on: the first two register slots are requested before the counts have arrived (a region is at least
 // 2 * threads slots long; what lies behind nb is ignored).  A bucket of more than capb pairs first collects its pairs
 // (the region + its share of the segment's overflow pool) into `gathered` and carries on from there.
-// the LDS of one bucket (owned by the kernel that calls bucket_body)
-struct BucketLds {
-    unsigned long long* tile;   // [CAP]
-    unsigned int* binarr;       // [LOBINS + 4] at a 16-B boundary: cur = binarr + 3 (cur[0] stays 0), bin d lives at cur[d + 1]
-    unsigned int* wsum;         // [BKT_WAVES]
-    unsigned int* roff;         // [MAXR + 1] pairs of the bucket in runs 0 .. c-1
-    unsigned int* rbase;        // [MAXR + 1] first pair of run c, as an index into the segment's pairs; [MAXR]: start
-    unsigned int* front;        // [BKT_WAVES + 1] REGION: per-wave sums of the counts in front; [BKT_WAVES]: gather cursor
-};
-template <int CAP, bool EMBED, int MAXR, bool REGION, bool LEAN>
+// MAXR = chunks whose run offsets fit the kernel's LDS table (64: every wave builds the table by itself with one
+// shuffle scan, no barrier; the large-tile kernel takes up to 1024 chunks = 4 M keys per segment through a serial
+// scan); longer segments walk the global table for every lookup -- slow, never wrong
+// (registers: the REGION kernel sits at 65 VGPRs = 7 waves per SIMD; at 64 its residency rises and the pileup-8clouds
+//  sort slows from 46.6 to 47.0 us -- look at the kernel's resource usage after touching this function)
+template <int CAP, bool EMBED, int MAXR, bool REGION>
 __device__ __forceinline__ void bucket_body(const unsigned long long* __restrict__ pairs,
                                             unsigned long long* __restrict__ scratch,
                                             const SegParams* __restrict__ seg_params,
                                             const unsigned int* __restrict__ tab, int N, int n_chunks,
-                                            int* __restrict__ pos_out, const RegionArgs& rga, const int seg, const int bucket,
-                                            const BucketLds& lds) {
+                                            int* __restrict__ pos_out, const RegionArgs& rga, const int seg, const int bucket) {
     static_assert(CAP >= LOBINS, "the tile also holds the splitters of the streaming path");
-    unsigned long long* tile_s = lds.tile;
-    unsigned int* cur_s = lds.binarr + 3;
-    unsigned int* wsum_s = lds.wsum;
-    unsigned int* roff_s = lds.roff;
-    unsigned int* rbase_s = lds.rbase;
-    unsigned int* front_s = lds.front;
+    static_assert(EMBED || !REGION, "the lean path reads the low id bits from the pair");
+    __shared__ unsigned long long tile_s[CAP];
+    // cur = binarr + 3 (cur[0] stays 0), bin d lives at cur[d + 1]: the bins start at a 16-B boundary
+    __shared__ __attribute__((aligned(16))) unsigned int binarr_s[LOBINS + 4];
+    __shared__ unsigned int wsum_s[BKT_WAVES];
+    __shared__ unsigned int roff_s[REGION ? 1 : MAXR + 1];    // pairs of the bucket in runs 0 .. c-1
+    __shared__ unsigned int rbase_s[REGION ? 1 : MAXR + 1];   // first pair of run c, as an index into the segment's pairs; [MAXR]: start
+    __shared__ unsigned int front_s[REGION ? BKT_WAVES + 1 : 1];   // REGION: per-wave sums of the counts in front; [BKT_WAVES]: gather cursor
+    unsigned int* cur_s = binarr_s + 3;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const unsigned long long* seg_pairs = pairs + (size_t)seg * N;
     const unsigned int* btab = tab + (size_t)seg * n_chunks * TAB + bucket;   // + c * TAB: [first, end) of run c
@@ -768,20 +638,16 @@ __device__ __forceinline__ void bucket_body(const unsigned long long* __restrict
         __syncthreads();   // the waves' sums of the counts in front (and the bins are zero in every wave's view)
 #pragma unroll
         for (int ww = 0; ww < BKT_WAVES; ++ww) start += (int)front_s[ww];
-#ifndef HEPT_BKT_NO_LEAN
-        if constexpr (EMBED && LEAN) {
-            if (nb <= LEAN_SLOTS * BKT_THREADS) {   // uniform: the common bucket
-                unsigned long long pr[LEAN_SLOTS];
+        if (nb <= LEAN_SLOTS * BKT_THREADS) {   // uniform: the common bucket
+            unsigned long long pr[LEAN_SLOTS];
 #pragma unroll
-                for (int u = 0; u < LEAN_SLOTS; ++u) {
-                    if (u >= SPEC && u * BKT_THREADS >= nb) break;   // uniform
-                    pr[u] = u < SPEC ? spec[u < SPEC ? u : 0] : (u * BKT_THREADS + tid < nb ? src[u * BKT_THREADS + tid] : 0ull);
-                }
-                bucket_lean(pr, nb, __builtin_amdgcn_readfirstlane(start), tile_s, cur_s, wsum_s, pos_out + (size_t)seg * N);
-                return;
+            for (int u = 0; u < LEAN_SLOTS; ++u) {
+                if (u >= SPEC && u * BKT_THREADS >= nb) break;   // uniform
+                pr[u] = u < SPEC ? spec[u < SPEC ? u : 0] : (u * BKT_THREADS + tid < nb ? src[u * BKT_THREADS + tid] : 0ull);
             }
+            bucket_lean(pr, nb, __builtin_amdgcn_readfirstlane(start), tile_s, cur_s, wsum_s, pos_out + (size_t)seg * N);
+            return;
         }
-#endif
         if (nb > (int)rga.capb) {   // uniform, uncommon: region + this bucket's share of the overflow pool -> gathered
             start = __builtin_amdgcn_readfirstlane(start);
             unsigned long long* gdst = rga.gathered + (size_t)seg * N + start;
@@ -791,7 +657,7 @@ __device__ __forceinline__ void bucket_body(const unsigned long long* __restrict
             const unsigned long long* pool = rga.pool + (size_t)seg * N;
             for (int j = tid; j < n_pool; j += BKT_THREADS) {
                 const unsigned long long p = pool[j];
-                if ((int)(bucket_id((unsigned int)(p >> 32), sp.kmin, sp.scale) >> TOP_SHIFT) == bucket)
+                if ((int)(bucket_id<ID_BUCKETS>((unsigned int)(p >> 32), sp.kmin, sp.scale) >> TOP_SHIFT) == bucket)
                     gdst[rga.capb + atomicAdd(&front_s[BKT_WAVES], 1u)] = p;
             }
             __threadfence_block();
@@ -846,11 +712,7 @@ __device__ __forceinline__ void bucket_body(const unsigned long long* __restrict
     const int n_reg = nb < CAP ? nb : CAP;
     int lpr_log = 0;
     while ((2 << lpr_log) * n_chunks <= BKT_THREADS) ++lpr_log;
-#ifdef HEPT_BKT_NO_BY_RUN
-    const bool by_run = false;
-#else
     const bool by_run = !REGION && n_chunks <= HEPT_WAVE && n_chunks <= BKT_THREADS && longest <= (ITEMS << lpr_log);   // uniform
-#endif
     unsigned long long mine[ITEMS];
     unsigned long long vmask = 0;   // bit u: slot u holds a pair (ITEMS <= 64)
     // slots in use anywhere in the workgroup (uniform): the passes below stop there instead of stepping through the
@@ -895,7 +757,7 @@ __device__ __forceinline__ void bucket_body(const unsigned long long* __restrict
     auto lo_of = [&](unsigned long long p) -> unsigned int {
         if (in_lds)
             return EMBED ? ((unsigned int)p >> EMBED_SHIFT) & (unsigned int)(LOBINS - 1)
-                         : bucket_id((unsigned int)(p >> 32), rg.kmin, rg.scale) & (unsigned int)(LOBINS - 1);
+                         : bucket_id<ID_BUCKETS>((unsigned int)(p >> 32), rg.kmin, rg.scale) & (unsigned int)(LOBINS - 1);
         int lo = 0, hi = LOBINS;  // number of splitters <= p
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
@@ -903,23 +765,9 @@ __device__ __forceinline__ void bucket_body(const unsigned long long* __restrict
         }
         return (unsigned int)(lo > 0 ? lo - 1 : 0);
     };
-    auto prefix_bins = [&]() {  // exclusive prefix over the bins: thread owns bins BPT*tid .. BPT*tid + BPT - 1
+    auto prefix_bins = [&]() {
         __syncthreads();   // the histogram is complete
-        unsigned int c[BKT_BINS_PER_THREAD], tot = 0;
-#pragma unroll
-        for (int u = 0; u < BKT_BINS_PER_THREAD; ++u) { c[u] = bin_s[BKT_BINS_PER_THREAD * tid + u]; tot += c[u]; }
-        const unsigned int incl = hept_wave_scan_add(tot);
-        if (lane == 63) wsum_s[w] = incl;
-        __syncthreads();
-        unsigned int run = incl - tot;
-#pragma unroll
-        for (int ww = 0; ww < BKT_WAVES; ++ww)
-            if (ww < w) run += wsum_s[ww];
-#pragma unroll
-        for (int u = 0; u < BKT_BINS_PER_THREAD; ++u) {
-            bin_s[BKT_BINS_PER_THREAD * tid + u] = run;
-            run += c[u];
-        }
+        bucket_prefix_bins(bin_s, wsum_s);
         __syncthreads();
     };
     if constexpr (!REGION) __syncthreads();   // the bins are zero in every wave's view (REGION: the barrier of the front sums)
@@ -1032,22 +880,12 @@ __global__ __launch_bounds__(BKT_THREADS) void bucket_sort_kernel(const unsigned
                                                                   RowsJob rows, RegionArgs rga) {
     if ((int)blockIdx.y < rows.vy) {   // uniform: a rider workgroup (the first rows of the grid: dispatched first)
         const unsigned int wg = blockIdx.y * gridDim.x + blockIdx.x, n_wgs = (unsigned int)rows.vy * gridDim.x;
-        if (rows.H == 8) rows_rider<8>(rows, wg, n_wgs);
-        else rows_rider<0>(rows, wg, n_wgs);
+        if (rows.H == 8) rows_rider<8, BKT_WAVES>(rows, wg, n_wgs);
+        else rows_rider<0, BKT_WAVES>(rows, wg, n_wgs);
         return;
     }
-#ifdef HEPT_RIDERS_ONLY   // measurement builds: what the riders cost by themselves
-    if (rows.vy > 0) return;
-#endif
-    __shared__ unsigned long long tile_s[CAP];
-    __shared__ __attribute__((aligned(16))) unsigned int binarr_s[LOBINS + 4];
-    __shared__ unsigned int wsum_s[BKT_WAVES];
-    __shared__ unsigned int roff_s[REGION ? 1 : MAXR + 1];
-    __shared__ unsigned int rbase_s[REGION ? 1 : MAXR + 1];
-    __shared__ unsigned int front_s[REGION ? BKT_WAVES + 1 : 1];
-    const BucketLds lds{tile_s, binarr_s, wsum_s, roff_s, rbase_s, front_s};
-    bucket_body<CAP, EMBED, MAXR, REGION, true>(pairs, scratch, seg_params, tab, N, n_chunks, pos_out, rga,
-                                                (int)blockIdx.y - rows.vy, (int)blockIdx.x, lds);
+    bucket_body<CAP, EMBED, MAXR, REGION>(pairs, scratch, seg_params, tab, N, n_chunks, pos_out, rga,
+                                          (int)blockIdx.y - rows.vy, (int)blockIdx.x);
 }
 
 // src variant: per (table, head) upper bound of the shift in units of span: max_n (phi * cfac + eta), written into
@@ -1071,7 +909,7 @@ __global__ __launch_bounds__(SORT_THREADS) void src_bound_kernel(const float* __
     __syncthreads();
     if (tid == 0) {
         m = fmaxf(fmaxf(red_s[0], red_s[1]), fmaxf(red_s[2], red_s[3]));
-        minmax[(((size_t)t * H + h) * HEPT_PREP_GRID + 0) * 4 + 2] = m * 1.0001f + 1.f;  // slack for the roundings
+        minmax[(((size_t)t * H + h) * HEPT_PREP_GRID + 0) * 4 + 2] = src_shift_bound(m);
     }
 }
 
@@ -1197,32 +1035,15 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(
                 const float e = eta_idx[row_off + i], p = phi_idx[row_off + i];
                 if (e < INFINITY && p < INFINITY) m = fmaxf(m, fmaf(p, cf, e));
             }
-            cmax = m * 1.0001f + 1.f;
+            cmax = src_shift_bound(m);
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off));
-        hi = fmaxf(hi, __shfl_xor(hi, off));
-        cmax = fmaxf(cmax, __shfl_xor(cmax, off));
-    }
-    if (lane == 0) { red_s[0][w] = lo; red_s[1][w] = hi; red_s[2][w] = cmax; }
-    __syncthreads();
-    lo = red_s[0][0]; hi = red_s[1][0]; cmax = red_s[2][0];
-#pragma unroll
-    for (int ww = 1; ww < SMALL_WAVES; ++ww) {
-        lo = fminf(lo, red_s[0][ww]); hi = fmaxf(hi, red_s[1][ww]); cmax = fmaxf(cmax, red_s[2][ww]);
-    }
+    reduce_range(lo, hi, cmax, red_s);
     if (lo > hi) { lo = 0.f; hi = 0.f; }  // no finite key at all
     const float span = hi - lo;
     const float width = MODE == 2 ? span : (hi + cmax * span) - lo;
-    float scale = width > 0.f ? (float)SMALL_BINS / width : 0.f;
-    if (!(scale < 3.0e38f)) scale = 0.f;
-    auto bin_of = [&](unsigned int u) -> unsigned int {
-        const float x = fminf((from_ordered(u) - lo) * scale, (float)(SMALL_BINS - 1));
-        const int b = (int)x;
-        return (unsigned int)(b < 0 ? 0 : b);
-    };
+    const float scale = id_scale(width, SMALL_BINS);
+    auto bin_of = [&](unsigned int u) { return bucket_id<SMALL_BINS>(u, lo, scale); };
 
     // ---- keys -> pairs in registers, histogram of the id
     unsigned long long mine[SMALL_ITEMS];
@@ -1235,23 +1056,9 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(
         mine[u] = ~0ull;   // (not a pair of this workgroup)
         if (n < N) {
             float key;
-            if (MODE == 0) {
-                float off = (float)cd0[u] * span;   // two separately rounded ops, as in K1
-                asm volatile("" : "+v"(off));
-                key = pj0[u] + off;
-            } else if (MODE == 1) {
-                float t1 = eta_idx[row_off + n] * span;
-                asm volatile("" : "+v"(t1));
-                float t2 = phi_idx[row_off + n] * span;
-                asm volatile("" : "+v"(t2));
-                t2 = t2 * cf;
-                asm volatile("" : "+v"(t2));
-                float t3 = t2 + t1;
-                asm volatile("" : "+v"(t3));
-                key = proj[n] + t3;
-            } else {
-                key = proj[n];
-            }
+            if constexpr (MODE == 0) key = sort_key(pj0[u], cd0[u], span);
+            else if constexpr (MODE == 1) key = sort_key(proj[n], eta_idx[row_off + n], phi_idx[row_off + n], cf, span);
+            else key = proj[n];
             const unsigned int ub = ordered_bits(key);
             const unsigned int b = bin_of(ub);
             if (Q == 1 || b / BQ == (unsigned int)part) {
@@ -1267,30 +1074,17 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(
         if (lane == 0) below_s[w] = below;
     }
     __syncthreads();
-    unsigned int n_mine;   // pairs of this workgroup
-    {   // exclusive prefix over the bins: thread owns BPT consecutive bins
-        constexpr int BPT = BQ / SMALL_THREADS;
-        unsigned int c[BPT], tot = 0;
+    constexpr int BPT = BQ / SMALL_THREADS;   // thread owns BPT consecutive bins (at cur_s + 1: no 16-B boundary)
+    unsigned int c[BPT];
 #pragma unroll
-        for (int u = 0; u < BPT; ++u) { c[u] = bin_s[BPT * tid + u]; tot += c[u]; }
-        const unsigned int incl = hept_wave_scan_add(tot);
-        if (lane == 63) wsum_s[w] = incl;
-        __syncthreads();
-        unsigned int run = incl - tot;
-        n_mine = 0;
-        below = 0;
+    for (int u = 0; u < BPT; ++u) c[u] = bin_s[BPT * tid + u];
+    unsigned int n_mine = exclusive_prefix<BPT, SMALL_WAVES>(c, wsum_s);   // pairs of this workgroup
 #pragma unroll
-        for (int ww = 0; ww < SMALL_WAVES; ++ww) {
-            const unsigned int ws = wsum_s[ww];
-            run += ww < w ? ws : 0u;
-            n_mine += ws;
-            if (Q > 1) below += below_s[ww];
-        }
+    for (int u = 0; u < BPT; ++u) bin_s[BPT * tid + u] = c[u];
+    below = 0;
+    if (Q > 1) {
 #pragma unroll
-        for (int u = 0; u < BPT; ++u) {
-            bin_s[BPT * tid + u] = run;
-            run += c[u];
-        }
+        for (int ww = 0; ww < SMALL_WAVES; ++ww) below += below_s[ww];
     }
     __syncthreads();
 #pragma unroll
@@ -1346,24 +1140,42 @@ __global__ __launch_bounds__(SMALL_THREADS) void small_sort_kernel(
     }
 }
 
+inline bool env_flag(const char* name) {   // set and not "0"
+    const char* e = getenv(name);
+    return e && *e && *e != '0';
+}
+
+// Where the keys of a call come from, filled once per entry point and unpacked at the launches.  MODE 0: qproj / kproj,
+// codes, minmax;  MODE 1: qproj / kproj, eta / phi / cfac, minmax;  MODE 2: qproj = the raw keys, their range from
+// range_bits (raw_range_kernel) or, where that is null, the caller's bounds [range_lo, range_hi].
+struct KeySrc {
+    const float *qproj, *kproj;
+    const int64_t* codes;
+    const float *eta, *phi, *cfac;
+    const float* minmax;
+    const unsigned int* range_bits;
+    float range_lo, range_hi;
+    int N, H, t0, Tl;      // N = segment stride
+    const int* seg_len;    // ragged argsort (or null: N keys per segment)
+};
+
 template <int MODE>
-int launch_small_sort(int segs, hipStream_t st, const float* qproj, const float* kproj, const int64_t* codes,
-                      const float* eta, const float* phi, const float* cfac, const float* minmax, int N, int H, int t0,
-                      int Tl, int* pos, const int* seg_len = nullptr) {
+int launch_small_sort(int segs, hipStream_t st, const KeySrc& ks, int* pos) {
     // one workgroup per segment when the launch already fills the chip, or when the segments are too short to be worth
     // splitting (HEPT_SMALL_NO_SPLIT=1: always; A/B runs)
-    static const bool no_split = [] { const char* e = getenv("HEPT_SMALL_NO_SPLIT"); return e && *e && *e != '0'; }();
+    static const bool no_split = env_flag("HEPT_SMALL_NO_SPLIT");
+    const int N = ks.N;
     if (SMALL_SPLIT > 1 && !no_split && segs <= 128 && N > SMALL_THREADS) {
         static LdsRaised raised;
         if (hept_raise_lds(raised, reinterpret_cast<const void*>(small_sort_kernel<MODE, SMALL_SPLIT>), SMALL_LDS)) return HEPT_ERR_LAUNCH;
         hipLaunchKernelGGL((small_sort_kernel<MODE, SMALL_SPLIT>), dim3(segs * SMALL_SPLIT), dim3(SMALL_THREADS), SMALL_LDS, st,
-                           qproj, kproj, codes, eta, phi, cfac, minmax, N, H, t0, Tl, pos, seg_len);
+                           ks.qproj, ks.kproj, ks.codes, ks.eta, ks.phi, ks.cfac, ks.minmax, N, ks.H, ks.t0, ks.Tl, pos, ks.seg_len);
         return hept_launch_status();
     }
     static LdsRaised raised1;
     if (hept_raise_lds(raised1, reinterpret_cast<const void*>(small_sort_kernel<MODE, 1>), SMALL_LDS)) return HEPT_ERR_LAUNCH;
-    hipLaunchKernelGGL((small_sort_kernel<MODE, 1>), dim3(segs), dim3(SMALL_THREADS), SMALL_LDS, st, qproj, kproj, codes, eta,
-                       phi, cfac, minmax, N, H, t0, Tl, pos, seg_len);
+    hipLaunchKernelGGL((small_sort_kernel<MODE, 1>), dim3(segs), dim3(SMALL_THREADS), SMALL_LDS, st, ks.qproj, ks.kproj, ks.codes,
+                       ks.eta, ks.phi, ks.cfac, ks.minmax, N, ks.H, ks.t0, ks.Tl, pos, ks.seg_len);
     return hept_launch_status();
 }
 
@@ -1378,7 +1190,7 @@ struct SortBuffers {
     size_t bytes;
 };
 inline bool region_sort_off() {   // HEPT_SORT_LINEAR=1: the round-3 layout (chunk runs + run tables) for A/B runs; read once
-    static const bool off = [] { const char* e = getenv("HEPT_SORT_LINEAR"); return e && *e && *e != '0'; }();
+    static const bool off = env_flag("HEPT_SORT_LINEAR");
     return off;
 }
 inline bool region_range(int N) { return N > SMALL_CAP && N <= REGION_MAX_N; }
@@ -1418,68 +1230,52 @@ __global__ __launch_bounds__(256) void zero_words_kernel(unsigned int* __restric
 constexpr int BKT_CAP_SMALL = HEPT_BKT_CAP;  // LDS tile: the average bucket is N/NTOP
 constexpr int BKT_CAP_LARGE = 6 * HEPT_BKT_CAP;  // 48 KiB tile for longer segments (average bucket up to ~3000 pairs)
 static_assert(REGION_MAX_N == NTOP * (BKT_CAP_SMALL / 2), "the REGION layout serves exactly the small-tile bucket kernel");
+// ... and both lie inside EMBED's range: only the large-tile kernel exists without the embedded low id bits
+static_assert(REGION_MAX_N <= (1 << EMBED_SHIFT), "REGION and the small tile are instantiated with EMBED only");
+template <int MODE, bool EMBED, bool REGION>
+void launch_chunk_sort(const SortBuffers& b, int segs, const KeySrc& ks, hipStream_t st) {
+    const int n_chunks = (ks.N + SORT_CHUNK - 1) / SORT_CHUNK;
+    hipLaunchKernelGGL((chunk_sort_kernel<MODE, EMBED, REGION>), dim3(n_chunks, segs), dim3(SCT), 0, st, ks.qproj, ks.kproj,
+                       ks.codes, ks.eta, ks.phi, ks.cfac, ks.minmax, ks.range_bits, ks.range_lo, ks.range_hi, ks.N, ks.H, ks.t0,
+                       ks.Tl, n_chunks, ks.seg_len, b.params, b.pa, b.tab, REGION ? b.rg : RegionArgs{});
+    if (MODE != 2) hept_prof_mark_sort_mid(st);
+}
 // `zeroed`: the caller has already zeroed b.zero_bytes at b.rg.cnt on this stream (the row builder of the same forward)
 template <int MODE, bool EMBED>
-int run_passes_impl(const SortBuffers& b, int segs, int N, int* pos, hipStream_t st, const float* qproj,
-                    const float* kproj, const int64_t* codes, const float* eta, const float* phi, const float* cfac,
-                    const float* minmax, int H, int t0, int Tl, const int* seg_len, const float* bounds,
-                    const RowsJob& rows, bool zeroed) {
-    const int n_chunks = (N + SORT_CHUNK - 1) / SORT_CHUNK;
+void run_passes_impl(const SortBuffers& b, int segs, const KeySrc& ks, int* pos, hipStream_t st, const RowsJob& rows, bool zeroed) {
+    const int N = ks.N, n_chunks = (N + SORT_CHUNK - 1) / SORT_CHUNK;
     const dim3 grid4(NTOP, segs + rows.vy);   // rider rows first
-    if (b.rg.region && !region_sort_off()) {
-        // (a caller whose preceding kernel did not clear the counters: a 48-workgroup kernel of our own -- the runtime's
-        //  fill kernel took 4.9 us for these 49 KB)
-        if (!zeroed) {
-            const unsigned int words = (unsigned int)(b.zero_bytes / 4);
-            hipLaunchKernelGGL(zero_words_kernel, dim3((words + 255) / 256), dim3(256), 0, st, b.rg.cnt, words);
-        }
-        hipLaunchKernelGGL((chunk_sort_kernel<MODE, EMBED, true>), dim3(n_chunks, segs), dim3(SCT), 0, st, qproj, kproj, codes,
-                           eta, phi, cfac, minmax, bounds ? nullptr : b.range, bounds ? bounds[0] : 0.f,
-                           bounds ? bounds[1] : 0.f, N, H, t0, Tl, n_chunks, seg_len, b.params, b.pa, b.tab, b.rg);
-        if (MODE != 2) hept_prof_mark_sort_mid(st);
-        hipLaunchKernelGGL((bucket_sort_kernel<BKT_CAP_SMALL, EMBED, 64, true>), grid4, dim3(BKT_THREADS), 0, st, b.pa, b.pb,
+    if constexpr (EMBED) {
+        if (b.rg.region && !region_sort_off()) {
+            // (a caller whose preceding kernel did not clear the counters: a 48-workgroup kernel of our own -- the runtime's
+            //  fill kernel took 4.9 us for these 49 KB)
+            if (!zeroed) {
+                const unsigned int words = (unsigned int)(b.zero_bytes / 4);
+                hipLaunchKernelGGL(zero_words_kernel, dim3((words + 255) / 256), dim3(256), 0, st, b.rg.cnt, words);
+            }
+            launch_chunk_sort<MODE, EMBED, true>(b, segs, ks, st);
+            hipLaunchKernelGGL((bucket_sort_kernel<BKT_CAP_SMALL, EMBED, 64, true>), grid4, dim3(BKT_THREADS), 0, st, b.pa, b.pb,
                                b.params, b.tab, N, n_chunks, pos, rows, b.rg);
-        return HEPT_OK;
+            return;
+        }
     }
-    hipLaunchKernelGGL((chunk_sort_kernel<MODE, EMBED, false>), dim3(n_chunks, segs), dim3(SCT), 0, st, qproj, kproj, codes, eta,
-                       phi, cfac, minmax, bounds ? nullptr : b.range, bounds ? bounds[0] : 0.f, bounds ? bounds[1] : 0.f, N,
-                       H, t0, Tl, n_chunks, seg_len, b.params, b.pa, b.tab, RegionArgs{});
-    if (MODE != 2) hept_prof_mark_sort_mid(st);
-    if ((size_t)N <= (size_t)NTOP * (BKT_CAP_SMALL / 2))
-        hipLaunchKernelGGL((bucket_sort_kernel<BKT_CAP_SMALL, EMBED, 64, false>), grid4, dim3(BKT_THREADS), 0, st, b.pa, b.pb, b.params,
-                           b.tab, N, n_chunks, pos, rows, RegionArgs{});
-    else
-        hipLaunchKernelGGL((bucket_sort_kernel<BKT_CAP_LARGE, EMBED, 1024, false>), grid4, dim3(BKT_THREADS), 0, st, b.pa, b.pb,
-                           b.params, b.tab, N, n_chunks, pos, rows, RegionArgs{});
-    return HEPT_OK;
+    launch_chunk_sort<MODE, EMBED, false>(b, segs, ks, st);
+    if constexpr (EMBED) {
+        if ((size_t)N <= (size_t)NTOP * (BKT_CAP_SMALL / 2)) {
+            hipLaunchKernelGGL((bucket_sort_kernel<BKT_CAP_SMALL, EMBED, 64, false>), grid4, dim3(BKT_THREADS), 0, st, b.pa, b.pb,
+                               b.params, b.tab, N, n_chunks, pos, rows, RegionArgs{});
+            return;
+        }
+    }
+    hipLaunchKernelGGL((bucket_sort_kernel<BKT_CAP_LARGE, EMBED, 1024, false>), grid4, dim3(BKT_THREADS), 0, st, b.pa, b.pb,
+                       b.params, b.tab, N, n_chunks, pos, rows, RegionArgs{});
 }
 template <int MODE>
-int run_passes(const SortBuffers& b, int segs, int N, int* pos, hipStream_t st, const float* qproj, const float* kproj,
-               const int64_t* codes, const float* eta, const float* phi, const float* cfac, const float* minmax, int H,
-               int t0, int Tl, const int* seg_len = nullptr, const float* bounds = nullptr,
-               const RowsJob& rows = RowsJob{}, bool zeroed = false) {
-    if (N <= (1 << EMBED_SHIFT))
-        return run_passes_impl<MODE, true>(b, segs, N, pos, st, qproj, kproj, codes, eta, phi, cfac, minmax, H, t0, Tl, seg_len,
-                                           bounds, rows, zeroed);
-    return run_passes_impl<MODE, false>(b, segs, N, pos, st, qproj, kproj, codes, eta, phi, cfac, minmax, H, t0, Tl, seg_len,
-                                        bounds, rows, zeroed);
-}
-
-// the job of the rider workgroups, from the description a caller in another translation unit hands over
-RowsJob rows_job(const HeptRowsJob* r) {
-    RowsJob jb{};
-    if (!r) return jb;
-    jb.v = r->v;
-    jb.kvhat = reinterpret_cast<char*>(r->kvhat);
-    jb.N = r->N;
-    jb.raw_size = r->raw_size;
-    jb.H = r->H;
-    jb.D4 = r->D / 4;
-    jb.f32 = hept_f32_rows(r->precision) ? 1 : 0;
-    static const int vy = [] { const char* e = getenv("HEPT_ROW_RIDERS"); const int n = e ? atoi(e) : 0; return n > 0 && n <= 64 ? n : HEPT_ROWS_RIDERS; }();
-    jb.vy = vy;   // (HEPT_ROW_RIDERS=<grid rows>: tuning; read once)
-    jb.in = r->in_dtype;
-    return jb;
+int run_passes(const SortBuffers& b, int segs, const KeySrc& ks, int* pos, hipStream_t st, const RowsJob& rows = RowsJob{},
+               bool zeroed = false) {
+    if (ks.N <= (1 << EMBED_SHIFT)) run_passes_impl<MODE, true>(b, segs, ks, pos, st, rows, zeroed);
+    else run_passes_impl<MODE, false>(b, segs, ks, pos, st, rows, zeroed);
+    return hept_launch_status();
 }
 
 }  // namespace
@@ -1509,10 +1305,19 @@ bool hept_sort_carries_rows(int N, int H, int D) {
     return N > SMALL_CAP && (size_t)N <= (size_t)NTOP * (BKT_CAP_SMALL / 2) && D >= 4 && D % 4 == 0 && D <= 28 && H >= 1;
 }
 
-// 16-bit v rows reach the riders as 8-byte pieces
-static inline bool rows_in_ok(const HeptRowsJob* r) {
-    if (r->in_dtype == HEPT_IN_F32) return true;
-    return (r->in_dtype == HEPT_IN_BF16 || r->in_dtype == HEPT_IN_F16) && (reinterpret_cast<uintptr_t>(r->v) & 7) == 0;
+// the checks the two table sorts share; have_all: none of the entry's own pointers is null
+static int check_tables_call(bool have_all, int N, int H, int T, int t0, int Tl, const int32_t* qpos, const int32_t* kpos,
+                             const HeptRowsJob* rows) {
+    if (!have_all) return HEPT_ERR_ARG;
+    if (rows) {
+        // 16-bit v rows reach the riders as 8-byte pieces
+        const bool in_ok = rows->in_dtype == HEPT_IN_F32 || ((rows->in_dtype == HEPT_IN_BF16 || rows->in_dtype == HEPT_IN_F16) &&
+                                                             (reinterpret_cast<uintptr_t>(rows->v) & 7) == 0);
+        if (!rows->v || !rows->kvhat || rows->N != N || !hept_sort_carries_rows(N, rows->H, rows->D) || !in_ok) return HEPT_ERR_ARG;
+    }
+    if (N < 1 || H < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
+    if (kpos != qpos + (size_t)Tl * H * N) return HEPT_ERR_ARG;  // one (2,Tl,H,N) array: q then k
+    return HEPT_OK;
 }
 
 extern "C" int hept_sort_tables(const float* qproj, const float* kproj, const int64_t* codes, const float* minmax,
@@ -1525,18 +1330,15 @@ extern "C" int hept_sort_tables(const float* qproj, const float* kproj, const in
 int hept_sort_tables_rows(const float* qproj, const float* kproj, const int64_t* codes, const float* minmax, int N, int H,
                           int T, int t0, int Tl, void* sort_ws, int32_t* qpos, int32_t* kpos, const HeptRowsJob* rows,
                           void* stream, bool zeroed) {
-    if (!qproj || !kproj || !codes || !minmax || !sort_ws || !qpos || !kpos) return HEPT_ERR_ARG;
-    if (rows && (!rows->v || !rows->kvhat || rows->N != N || !hept_sort_carries_rows(N, rows->H, rows->D) || !rows_in_ok(rows))) return HEPT_ERR_ARG;
-    if (N < 1 || H < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
-    if (kpos != qpos + (size_t)Tl * H * N) return HEPT_ERR_ARG;  // one (2,Tl,H,N) array: q then k
+    if (const int rc = check_tables_call(qproj && kproj && codes && minmax && sort_ws && qpos && kpos, N, H, T, t0, Tl, qpos, kpos, rows))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const int segs = 2 * Tl * H;
-    if (N <= SMALL_CAP)
-        return launch_small_sort<0>(segs, st, qproj, kproj, codes, nullptr, nullptr, nullptr, minmax, N, H, t0, Tl, qpos);
-    const SortBuffers b = carve_sort(sort_ws, segs, N);
-    const int rc = run_passes<0>(b, segs, N, qpos, st, qproj, kproj, codes, nullptr, nullptr, nullptr, minmax, H, t0, Tl,
-                                 nullptr, nullptr, rows_job(rows), zeroed);
-    return rc ? rc : hept_launch_status();
+    KeySrc ks{};
+    ks.qproj = qproj; ks.kproj = kproj; ks.codes = codes; ks.minmax = minmax;
+    ks.N = N; ks.H = H; ks.t0 = t0; ks.Tl = Tl;
+    if (N <= SMALL_CAP) return launch_small_sort<0>(segs, st, ks, qpos);
+    return run_passes<0>(carve_sort(sort_ws, segs, N), segs, ks, qpos, st, rows_job(rows), zeroed);
 }
 
 extern "C" int hept_sort_tables_src(const float* qproj, const float* kproj, const float* eta_idx,
@@ -1549,21 +1351,18 @@ extern "C" int hept_sort_tables_src(const float* qproj, const float* kproj, cons
 int hept_sort_tables_src_rows(const float* qproj, const float* kproj, const float* eta_idx, const float* phi_idx,
                               const float* cfac, float* minmax, int N, int H, int T, int t0, int Tl, void* sort_ws,
                               int32_t* qpos, int32_t* kpos, const HeptRowsJob* rows, void* stream, bool zeroed) {
-    if (!qproj || !kproj || !eta_idx || !phi_idx || !cfac || !minmax || !sort_ws || !qpos || !kpos)
-        return HEPT_ERR_ARG;
-    if (rows && (!rows->v || !rows->kvhat || rows->N != N || !hept_sort_carries_rows(N, rows->H, rows->D) || !rows_in_ok(rows))) return HEPT_ERR_ARG;
-    if (N < 1 || H < 1 || Tl < 1 || Tl > HEPT_MAX_TABLES || t0 < 0 || t0 + Tl > T) return HEPT_ERR_SHAPE;
-    if (kpos != qpos + (size_t)Tl * H * N) return HEPT_ERR_ARG;
+    if (const int rc = check_tables_call(qproj && kproj && eta_idx && phi_idx && cfac && minmax && sort_ws && qpos && kpos, N, H, T,
+                                         t0, Tl, qpos, kpos, rows))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const int segs = 2 * Tl * H;
-    if (N <= SMALL_CAP)
-        return launch_small_sort<1>(segs, st, qproj, kproj, nullptr, eta_idx, phi_idx, cfac, minmax, N, H, t0, Tl, qpos);
-    const SortBuffers b = carve_sort(sort_ws, segs, N);
+    KeySrc ks{};
+    ks.qproj = qproj; ks.kproj = kproj; ks.eta = eta_idx; ks.phi = phi_idx; ks.cfac = cfac; ks.minmax = minmax;
+    ks.N = N; ks.H = H; ks.t0 = t0; ks.Tl = Tl;
+    if (N <= SMALL_CAP) return launch_small_sort<1>(segs, st, ks, qpos);
     hipLaunchKernelGGL(src_bound_kernel, dim3(Tl * H), dim3(SORT_THREADS), 0, st, eta_idx, phi_idx, cfac, N, H, t0,
                        minmax);
-    const int rc = run_passes<1>(b, segs, N, qpos, st, qproj, kproj, nullptr, eta_idx, phi_idx, cfac, minmax, H, t0, Tl,
-                                 nullptr, nullptr, rows_job(rows), zeroed);
-    return rc ? rc : hept_launch_status();
+    return run_passes<1>(carve_sort(sort_ws, segs, N), segs, ks, qpos, st, rows_job(rows), zeroed);
 }
 
 extern "C" size_t hept_argsort_workspace_bytes(int S, int L) { return sort_bytes((size_t)S, (size_t)L); }
@@ -1574,18 +1373,22 @@ int segmented_argsort_impl(const float* keys, int S, int L, const int* seg_len, 
     if (!keys || !ws || !pos) return HEPT_ERR_ARG;
     if (S < 1 || L < 1) return HEPT_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    if (L <= SMALL_CAP)
-        return launch_small_sort<2>(S, st, keys, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, L, 1, 0, 1, pos,
-                                    seg_len);
+    KeySrc ks{};
+    ks.qproj = keys;
+    ks.N = L; ks.H = 1; ks.t0 = 0; ks.Tl = 1;
+    ks.seg_len = seg_len;
+    if (L <= SMALL_CAP) return launch_small_sort<2>(S, st, ks, pos);
     const int n_chunks = (L + SORT_CHUNK - 1) / SORT_CHUNK;
     const SortBuffers b = carve_sort(ws, S, L);
-    if (!bounds) {   // the key range of every segment: two more launches that a caller with known bounds saves
+    if (bounds) {
+        ks.range_lo = bounds[0];
+        ks.range_hi = bounds[1];
+    } else {   // the key range of every segment: two more launches that a caller with known bounds saves
         if (hipMemsetAsync(b.range, 0xFF, (size_t)S * 8, st) != hipSuccess) return HEPT_ERR_LAUNCH;
         hipLaunchKernelGGL(raw_range_kernel, dim3(n_chunks, S), dim3(SORT_THREADS), 0, st, keys, L, seg_len, b.range);
+        ks.range_bits = b.range;
     }
-    const int rc = run_passes<2>(b, S, L, pos, st, keys, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, 1, seg_len,
-                                 bounds);
-    return rc ? rc : hept_launch_status();
+    return run_passes<2>(b, S, ks, pos, st);
 }
 }  // namespace
 

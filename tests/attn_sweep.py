@@ -128,7 +128,7 @@ def cells(s):
     nkt = -(-s.B // 32)                                            # csrc/block_attn.hip:786
     kind = "full" if s.B == 32 * nkt else "ragged"                 # launch_attn / launch_attn_split: B == 32 nkt
     out = {f"nkt{nkt}-{kind}", f"coords{s.C}",
-           "sort-two-launch" if n > SMALL_CAP else "sort-one-workgroup",   # csrc/sort_tables.hip:1449
+           "sort-two-launch" if n > SMALL_CAP else "sort-one-workgroup",   # csrc/sort_tables.hip:1340
            "table-chunks" if s.T > MAX_TABLES else "tables-one-chunk",          # csrc/capi.hip hept_attn_block_forward
            "combine-flat" if n >= CMB_FLAT_FROM else "combine-split",           # csrc/combine.hip combine_launch_impl
            "combine-last-tile-ragged" if n % 32 else "combine-last-tile-full",

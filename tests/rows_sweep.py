@@ -66,6 +66,10 @@ NORM_BOUND = 31 * 2.0 ** -24    # a 30-term float32 fmaf accumulation: gamma_30 
 TWO_ROLE_N = (10912, 10944, 16384, 16416, 32800)
 TWO_ROLE_GENERIC = (16416, (16, 24, 6))
 TWO_ROLE_PRECISIONS = ("fp32", "bf16", "mixed16")
+# the riders' 1.0 at column D (csrc/rows_rider.h), at TWO_ROLE_N[0]: D = 4 is the second quad of piece 0 of a 16-bit row
+# half, D = 20 of piece 2; H = 3: the run-time head count, with a trip that runs past the last head.  (D = 28, the last
+# piece of an f32 row half, cannot be reached: hept_check_shape refuses D > 27 for every H and C, csrc/capi.hip:284.)
+TWO_ROLE_COLUMN_D = ((3, 4, 3), (3, 20, 4))
 
 # file:line references of the rules cells() and prep_wgs() mirror (tests/test_rows_sweep_cells.py checks the text)
 REFS = [
@@ -601,7 +605,8 @@ def check_round(cell, dev):
 # ---------------------------------------------------------------------------------------------------------------------
 def two_role_cases():
     out = [(n, (8, 24, 6), p) for n in TWO_ROLE_N for p in TWO_ROLE_PRECISIONS]
-    return out + [(TWO_ROLE_GENERIC[0], TWO_ROLE_GENERIC[1], "fp32")]
+    out += [(TWO_ROLE_GENERIC[0], TWO_ROLE_GENERIC[1], "fp32")]
+    return out + [(TWO_ROLE_N[0], hdc, p) for hdc in TWO_ROLE_COLUMN_D for p in TWO_ROLE_PRECISIONS]
 
 
 def two_role_shape(n, hdc):

@@ -42,39 +42,39 @@ AUDIT = [
     ("ws.kvhat k half", "prep_role<ROLE 1> / prep_generic_kernel role 1", "prep_hash.hip:425,772",
      "block_attn kernels", "block_attn.hip:73,386", ""),
     ("ws.kvhat v half", "one of: row builder v role (roles == 3), rider workgroups of bucket_sort_kernel, nobody (direct v)",
-     "capi.hip:214-226, sort_tables.hip:1428", "block_attn kernels; direct v: block_attn_split_kernel reads the caller's v",
+     "capi.hip:214-226, sort_tables.hip:1247, rows_rider.h:73", "block_attn kernels; direct v: block_attn_split_kernel reads the caller's v",
      "block_attn.hip:386", "direct v: the v half keeps whatever the workspace held and must never be read (ff pattern = NaN)"),
     ("ws.qproj / ws.kproj", "row builder, q and k roles", "prep_hash.hip:744", "chunk_sort_kernel / small sort",
-     "sort_tables.hip:143,1187", "padding rows of the src variant get +inf"),
+     "sort_tables.hip:218,1025", "padding rows of the src variant get +inf"),
     ("ws.minmax [Tc][H][PREP_GRID][4]", "row builder: own slot + the filler loop for the slots of workgroups not launched",
-     "prep_hash.hip:466-468,792", "chunk_sort_kernel, small sort (read whole)", "sort_tables.hip:228,1190",
-     "4th float stored as 0; src: src_bound_kernel rewrites slot 0 column 2 (sort_tables.hip:1074) before KA reads it"),
+     "prep_hash.hip:466-468,792", "chunk_sort_kernel, small sort (read whole)", "sort_tables.hip:304,1028",
+     "4th float stored as 0; src: src_bound_kernel rewrites slot 0 column 2 (sort_tables.hip:912) before KA reads it"),
     ("ws.pos", "bucket_sort_kernel / small sort, or the chunk copy of walk_tables", "capi.hip:172-184",
      "block_attn kernels", "block_attn.hip:73", ""),
     ("ws.pos_chunk", "bucket_sort_kernel / small sort of one chunk", "capi.hip:172", "hipMemcpyAsync of walk_tables",
      "capi.hip:181", "only with more than HEPT_MAX_TABLES tables"),
     ("ws.part", "block_attn kernels (every row of every table)", "block_attn.hip:832", "combine / reduce kernels",
      "combine.hip:131,573,612", ""),
-    # ---- carve_sort(), csrc/sort_tables.hip:1385-1413
-    ("sort.pa / rg.pool", "chunk_sort_kernel (runs; REGION: overflow pairs behind the cursor)", "sort_tables.hip:143",
-     "bucket_sort_kernel", "sort_tables.hip:1049", "read only below the counts KA published"),
-    ("sort.pb", "bucket_sort_kernel (streaming scratch)", "sort_tables.hip:1049", "bucket_sort_kernel", "sort_tables.hip:1049", ""),
-    ("sort.tab", "chunk_sort_kernel", "sort_tables.hip:143", "bucket_sort_kernel", "sort_tables.hip:1049", ""),
-    ("sort.range", "hipMemsetAsync 0xFF, then raw_range_kernel atomicMin", "sort_tables.hip:1583,1112",
-     "chunk_sort_kernel<MODE 2>", "sort_tables.hip:211", "segmented_argsort only; skipped with caller bounds"),
-    ("sort.params", "chunk_sort_kernel, chunk 0", "sort_tables.hip:254", "bucket_sort_kernel", "sort_tables.hip:1049", ""),
+    # ---- carve_sort(), csrc/sort_tables.hip:1197-1195
+    ("sort.pa / rg.pool", "chunk_sort_kernel (runs; REGION: overflow pairs behind the cursor)", "sort_tables.hip:217",
+     "bucket_sort_kernel", "sort_tables.hip:875", "read only below the counts KA published"),
+    ("sort.pb", "bucket_sort_kernel (streaming scratch)", "sort_tables.hip:875", "bucket_sort_kernel", "sort_tables.hip:875", ""),
+    ("sort.tab", "chunk_sort_kernel", "sort_tables.hip:217", "bucket_sort_kernel", "sort_tables.hip:875", ""),
+    ("sort.range", "hipMemsetAsync 0xFF, then raw_range_kernel atomicMin", "sort_tables.hip:1387,950",
+     "chunk_sort_kernel<MODE 2>", "sort_tables.hip:288", "segmented_argsort only; skipped with caller bounds"),
+    ("sort.params", "chunk_sort_kernel, chunk 0", "sort_tables.hip:317", "bucket_sort_kernel", "sort_tables.hip:875", ""),
     ("sort.rg.cnt + cursors (zero block)", "zero_block of the row builder (3 call sites) or zero_words_kernel",
-     "prep_hash.hip:137,514,558,682; sort_tables.hip:1432-1435", "chunk_sort_kernel atomicAdd", "sort_tables.hip:298,362",
+     "prep_hash.hip:137,514,558,682; sort_tables.hip:1252-1255", "chunk_sort_kernel atomicAdd", "sort_tables.hip:346,409",
      "size recomputed per table chunk (capi.hip:165-168) from the same carve_sort(2 tc H, N) the sort uses"),
-    ("sort.rg.region / rg.gathered", "chunk_sort_kernel / bucket_sort_kernel", "sort_tables.hip:298,795",
-     "bucket_sort_kernel", "sort_tables.hip:1049", "read only below cnt"),
+    ("sort.rg.region / rg.gathered", "chunk_sort_kernel / bucket_sort_kernel", "sort_tables.hip:346,661",
+     "bucket_sort_kernel", "sort_tables.hip:875", "read only below cnt"),
     # ---- buffers of the Python layer
     ("ops._row_buffers qhat/kvhat/qproj/kproj/minmax", "row builder, all three roles (stage call: roles == 3)",
      "prep_hash.hip:878-948", "sort / block_attn stage calls", "ops.py:276,332", "rows= reuses the buffers: rewritten identically"),
-    ("ops.sort_tables ws, pos", "zero_words_kernel + chunk_sort_kernel; sort kernels", "sort_tables.hip:1432",
-     "bucket_sort_kernel; caller", "sort_tables.hip:1049", "stand-alone zero path"),
-    ("ops.segmented_argsort ws, pos", "memset + raw_range_kernel + sort kernels", "sort_tables.hip:1583",
-     "sort kernels; caller", "sort_tables.hip:211", "ragged: pos[s, lens[s]:] is documented undefined and not written"),
+    ("ops.sort_tables ws, pos", "zero_words_kernel + chunk_sort_kernel; sort kernels", "sort_tables.hip:1252",
+     "bucket_sort_kernel; caller", "sort_tables.hip:875", "stand-alone zero path"),
+    ("ops.segmented_argsort ws, pos", "memset + raw_range_kernel + sort kernels", "sort_tables.hip:1387",
+     "sort kernels; caller", "sort_tables.hip:288", "ragged: pos[s, lens[s]:] is documented undefined and not written"),
     ("ops.block_attn part", "block_attn kernels", "block_attn.hip:840", "caller", "ops.py:347", ""),
     ("ops.reduce_tables / _forward_partial acc", "reduce_tables_kernel or block_attn (one table, same format)",
      "combine.hip:573, capi.hip:294", "caller", "ops.py:380,575", ""),

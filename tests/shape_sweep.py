@@ -14,8 +14,8 @@ import torch
 Shape = namedtuple("Shape", "id sizes B T H D C seed bwd")
 
 MAX_TABLES = 8          # HEPT_MAX_TABLES (include/hept_hip.h): prep_hash and the sort take at most this many tables
-SMALL_CAP = 6144        # csrc/sort_tables.hip:1045: N <= SMALL_CAP sorts each segment in one workgroup
-REGION_MAX_N = 131072   # csrc/sort_tables.hip:99: the small-tile bucket kernel's range (the riders' range)
+SMALL_CAP = 6144        # csrc/sort_tables.hip:961: N <= SMALL_CAP sorts each segment in one workgroup
+REGION_MAX_N = 131072   # csrc/sort_tables.hip:179: the small-tile bucket kernel's range (the riders' range)
 TUNED = [(24, 6), (24, 4), (24, 2), (16, 6), (16, 4), (8, 4)]   # H = 8 with these: csrc/prep_hash.hip:802-807
 FREE = [(4, 24, 6), (16, 24, 6), (16, 12, 3), (2, 27, 3), (5, 20, 5), (12, 8, 4), (1, 24, 6), (3, 10, 6), (16, 16, 4),
         (7, 17, 3)]     # the free head shapes of tests/op_stress.py
@@ -114,7 +114,7 @@ BWD_SHAPES = [s for s in SHAPES if s.bwd]
 
 def riders(n, h, d, t, precision, b):
     """run_begin (csrc/capi.hip:135-138): the bucket-sort launch writes the v rows (hept_sort_carries_rows,
-    csrc/sort_tables.hip:1429) unless the f32 split kernel reads v in place (direct v)."""
+    csrc/sort_tables.hip:1304) unless the f32 split kernel reads v in place (direct v)."""
     carries = SMALL_CAP < n <= REGION_MAX_N and 4 <= d <= 28 and d % 4 == 0 and h >= 1
     f32_rows = precision.startswith("fp32")
     return not direct_v(d, precision, b) and t <= MAX_TABLES and (t >= 2 or f32_rows) and carries
@@ -130,7 +130,7 @@ def cells(s):
     n = n_points(s)
     nkt = -(-s.B // 32)                                            # csrc/block_attn.hip:786
     out = {f"nkt{nkt}-{'full' if s.B == 32 * nkt else 'ragged'}",  # launch_attn / launch_attn_split: B == 32 nkt
-           "sort-two-launch" if n > SMALL_CAP else "sort-one-workgroup",   # csrc/sort_tables.hip:1449
+           "sort-two-launch" if n > SMALL_CAP else "sort-one-workgroup",   # csrc/sort_tables.hip:1340
            "rows-tuned" if s.H == 8 and (s.D, s.C) in TUNED else "rows-generic",   # csrc/prep_hash.hip:802
            "table-chunks" if s.T > MAX_TABLES else "tables-one-chunk",          # csrc/capi.hip:141-160
            "clouds-one" if len(s.sizes) == 1 else "clouds-several"}

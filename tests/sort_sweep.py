@@ -16,8 +16,8 @@ the wanted id's interval, on the 2^-16 grid) and verifies every population.  All
 the float32 key is exact however it is rounded and equals the float64 host key bit for bit.
 
 A cell is a list of hot buckets (population, how it spreads over the 512 low-id bins, which chunks it comes from) next to
-an ordinary background; ``stats`` runs the float32 mirror of the dispatch and of bucket_id / bin_of over the cell's actual
-inputs and returns the instantiations, per (segment, bucket) the population, the low-half count and the largest id
+an ordinary background; ``stats`` runs the float32 mirror of the dispatch and of bucket_id<BUCKETS> over the cell's
+actual inputs and returns the instantiations, per (segment, bucket) the population, the low-half count and the largest id
 group, and per (chunk, bucket) the run length; ``tags`` derives the branch names from those numbers alone."""
 import os
 import sys
@@ -51,35 +51,34 @@ def region_cap(n):
 
 # file:line references of the rules the mirror restates (tests/test_sort_sweep_cells.py checks the text)
 REFS = [
-    ("hept_amd/csrc/sort_tables.hip", 40, "constexpr int SORT_CHUNK = SORT_THREADS * SORT_ITEMS;"),
-    ("hept_amd/csrc/sort_tables.hip", 61, "if (key == 0.f) key = 0.f;"),
-    ("hept_amd/csrc/sort_tables.hip", 71, "fminf((from_ordered(u) - kmin) * scale, (float)(ID_BUCKETS - 1))"),
-    ("hept_amd/csrc/sort_tables.hip", 102, "while ((size_t)c * 32 < (size_t)N) c <<= 1;"),
-    ("hept_amd/csrc/sort_tables.hip", 172, "const bool vec_ok = (N % 4) == 0;"),
-    ("hept_amd/csrc/sort_tables.hip", 250, "const float width = (hi + cmax * span) - lo;"),
-    ("hept_amd/csrc/sort_tables.hip", 253, "if (!(scale < 3.0e38f)) scale = 0.f;"),
-    ("hept_amd/csrc/sort_tables.hip", 268, "float off = (float)cd[r] * span;"),
-    ("hept_amd/csrc/sort_tables.hip", 276, "t2 = t2 * cf;"),
-    ("hept_amd/csrc/sort_tables.hip", 331, "const unsigned int ov = end > rg.capb ? end - (gbase > rg.capb ? gbase : rg.capb) : 0u;"),
-    ("hept_amd/csrc/sort_tables.hip", 376, "pool[over_s[d] + (slot - (gb > rg.capb ? gb : rg.capb))] = stage_s[lp];"),
-    ("hept_amd/csrc/sort_tables.hip", 714, "if (n_chunks <= HEPT_WAVE) {"),
-    ("hept_amd/csrc/sort_tables.hip", 689, "const bool table_in_lds = REGION || n_chunks <= MAXR;"),
-    ("hept_amd/csrc/sort_tables.hip", 773, "if (nb <= LEAN_SLOTS * BKT_THREADS) {"),
-    ("hept_amd/csrc/sort_tables.hip", 785, "if (nb > (int)rga.capb) {"),
-    ("hept_amd/csrc/sort_tables.hip", 848, "while ((2 << lpr_log) * n_chunks <= BKT_THREADS) ++lpr_log;"),
-    ("hept_amd/csrc/sort_tables.hip", 852, "longest <= (ITEMS << lpr_log);"),
-    ("hept_amd/csrc/sort_tables.hip", 893, "bool in_lds = nb <= 2 * CAP;"),
-    ("hept_amd/csrc/sort_tables.hip", 937, "if (n_low > CAP || nb - n_low > CAP) in_lds = false;"),
-    ("hept_amd/csrc/sort_tables.hip", 1074, "= m * 1.0001f + 1.f;"),
-    ("hept_amd/csrc/sort_tables.hip", 1200, "cmax = m * 1.0001f + 1.f;"),
-    ("hept_amd/csrc/sort_tables.hip", 1219, "float scale = width > 0.f ? (float)SMALL_BINS / width : 0.f;"),
-    ("hept_amd/csrc/sort_tables.hip", 1257, "if (Q == 1 || b / BQ == (unsigned int)part) {"),
-    ("hept_amd/csrc/sort_tables.hip", 1356, "if (SMALL_SPLIT > 1 && !no_split && segs <= 128 && N > SMALL_THREADS) {"),
-    ("hept_amd/csrc/sort_tables.hip", 1384, "inline bool region_range(int N) { return N > SMALL_CAP && N <= REGION_MAX_N; }"),
-    ("hept_amd/csrc/sort_tables.hip", 1429, "if (b.rg.region && !region_sort_off()) {"),
-    ("hept_amd/csrc/sort_tables.hip", 1448, "if ((size_t)N <= (size_t)NTOP * (BKT_CAP_SMALL / 2))"),
-    ("hept_amd/csrc/sort_tables.hip", 1461, "if (N <= (1 << EMBED_SHIFT))"),
-    ("hept_amd/csrc/sort_tables.hip", 1534, "if (N <= SMALL_CAP)"),
+    ("hept_amd/csrc/sort_tables.hip", 41, "constexpr int SORT_CHUNK = SORT_THREADS * SORT_ITEMS;"),
+    ("hept_amd/csrc/sort_tables.hip", 62, "if (key == 0.f) key = 0.f;"),
+    ("hept_amd/csrc/sort_tables.hip", 73, "fminf((from_ordered(u) - kmin) * scale, (float)(BUCKETS - 1))"),
+    ("hept_amd/csrc/sort_tables.hip", 79, "float scale = width > 0.f ? (float)buckets / width : 0.f;"),
+    ("hept_amd/csrc/sort_tables.hip", 80, "if (!(scale < 3.0e38f)) scale = 0.f;"),
+    ("hept_amd/csrc/sort_tables.hip", 91, "float off = (float)code * span;"),
+    ("hept_amd/csrc/sort_tables.hip", 100, "t2 = t2 * cf;"),
+    ("hept_amd/csrc/sort_tables.hip", 107, "return m * 1.0001f + 1.f;"),
+    ("hept_amd/csrc/sort_tables.hip", 182, "while ((size_t)c * 32 < (size_t)N) c <<= 1;"),
+    ("hept_amd/csrc/sort_tables.hip", 249, "const bool vec_ok = (N % 4) == 0;"),
+    ("hept_amd/csrc/sort_tables.hip", 314, "const float width = (hi + cmax * span) - lo;"),
+    ("hept_amd/csrc/sort_tables.hip", 384, "const unsigned int ov = end > rg.capb ? end - (gbase > rg.capb ? gbase : rg.capb) : 0u;"),
+    ("hept_amd/csrc/sort_tables.hip", 423, "pool[over_s[d] + (slot - (gb > rg.capb ? gb : rg.capb))] = stage_s[lp];"),
+    ("hept_amd/csrc/sort_tables.hip", 584, "if (n_chunks <= HEPT_WAVE) {"),
+    ("hept_amd/csrc/sort_tables.hip", 559, "const bool table_in_lds = REGION || n_chunks <= MAXR;"),
+    ("hept_amd/csrc/sort_tables.hip", 641, "if (nb <= LEAN_SLOTS * BKT_THREADS) {"),
+    ("hept_amd/csrc/sort_tables.hip", 651, "if (nb > (int)rga.capb) {"),
+    ("hept_amd/csrc/sort_tables.hip", 714, "while ((2 << lpr_log) * n_chunks <= BKT_THREADS) ++lpr_log;"),
+    ("hept_amd/csrc/sort_tables.hip", 715, "longest <= (ITEMS << lpr_log);"),
+    ("hept_amd/csrc/sort_tables.hip", 755, "bool in_lds = nb <= 2 * CAP;"),
+    ("hept_amd/csrc/sort_tables.hip", 785, "if (n_low > CAP || nb - n_low > CAP) in_lds = false;"),
+    ("hept_amd/csrc/sort_tables.hip", 1064, "if (Q == 1 || b / BQ == (unsigned int)part) {"),
+    ("hept_amd/csrc/sort_tables.hip", 1168, "if (SMALL_SPLIT > 1 && !no_split && segs <= 128 && N > SMALL_THREADS) {"),
+    ("hept_amd/csrc/sort_tables.hip", 1196, "inline bool region_range(int N) { return N > SMALL_CAP && N <= REGION_MAX_N; }"),
+    ("hept_amd/csrc/sort_tables.hip", 1249, "if (b.rg.region && !region_sort_off()) {"),
+    ("hept_amd/csrc/sort_tables.hip", 1264, "if ((size_t)N <= (size_t)NTOP * (BKT_CAP_SMALL / 2))"),
+    ("hept_amd/csrc/sort_tables.hip", 1276, "if (ks.N <= (1 << EMBED_SHIFT))"),
+    ("hept_amd/csrc/sort_tables.hip", 1340, "if (N <= SMALL_CAP)"),
 ]
 
 ALL_TAGS = {"lean", "general-one-pass", "two-pass", "two-pass-refused-low", "two-pass-refused-high", "splitters",
@@ -89,9 +88,9 @@ ALL_TAGS = {"lean", "general-one-pass", "two-pass", "two-pass-refused-low", "two
 
 
 def all_instantiations():
-    """The reachable ones.  run_passes_impl also compiles chunk_sort_kernel<MODE, false, true> and
-    bucket_sort_kernel<1024, false, 64, *>: REGION and the small tile serve N <= 131 072 < 2^20 only, so no call selects
-    them."""
+    """The reachable ones, which are also the compiled ones: REGION and the small tile serve N <= 131 072 < 2^20 only,
+    so run_passes_impl instantiates chunk_sort_kernel<MODE, EMBED, true> and bucket_sort_kernel<1024, EMBED, 64, *>
+    with EMBED alone."""
     out = set()
     for mode in (0, 1, 2):
         out |= {("chunk", mode, True, True), ("chunk", mode, True, False), ("chunk", mode, False, False)}
@@ -315,7 +314,7 @@ def keys32(c, d, g):
 
 
 def ids_of(k32, lo, scale, bins):
-    """bucket_id / bin_of: (ids, keys whose scaled value lies at or beyond the id range)."""
+    """bucket_id<bins>: (ids, keys whose scaled value lies at or beyond the id range)."""
     with np.errstate(invalid="ignore", over="ignore"):
         x = (k32 - lo).astype(F) * scale
     x = np.where(np.isnan(x), F(bins - 1), x)                 # fminf(NaN, b) = b: inf * 0
@@ -361,7 +360,7 @@ def stats(c):
 
 
 def bucket_tags(dp, nb, n_low, runs):
-    """The branches one bucket of nb > 0 pairs takes in bucket_body."""
+    """The branches one bucket of nb > 0 pairs takes in bucket_sort_kernel."""
     out = set()
     cap = dp["cap"]
     if dp["layout"] == "region":

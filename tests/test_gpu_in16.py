@@ -115,6 +115,9 @@ CASES = {
     "d-riders-8B-source": ((6400,), 128, 2, 12, 12, 4, ("fp32", "bf16")),
     "e-direct-v-shape": ((512,), 256, 2, 8, 24, 6, ("fp32",)),
     "f-table-chunks": ((256,), 64, 9, 8, 24, 6, ("fp32", "bf16")),
+    # the riders' 1.0 at column D in the second quad of piece 0, with a run-time head count (rows_sweep.TWO_ROLE_COLUMN_D;
+    # D = 28 is refused by hept_check_shape)
+    "g-riders-d4": ((10912,), 32, 2, 3, 4, 3, ("fp32", "bf16", "mixed16")),
 }
 
 
@@ -127,6 +130,8 @@ def _branch_checks(name, n, b, t, h, d, c, precision):
         assert n > SMALL_CAP and not riders(n, h, d, t, precision, b) and not direct_v(d, precision, b)
     elif name.startswith("d-"):
         assert riders(n, h, d, t, precision, b) and d % 4 == 0 and (d * 2) % 16 == 8   # head rows start at 8-byte steps
+    elif name.startswith("g-"):
+        assert riders(n, h, d, t, precision, b) and (h, d) == (3, 4)
     elif name.startswith("e-"):
         assert direct_v(d, precision, b)      # what the f32 inputs take; 16-bit inputs must fall back to built rows
     elif name.startswith("f-"):

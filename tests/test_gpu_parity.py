@@ -308,7 +308,7 @@ def test_edge_cases(gpu_device):
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_v_rows_written_by_the_bucket_sort_launch(precision, gpu_device):
     """Clouds longer than the one-workgroup sort: the v half of the kvhat rows is written by rider workgroups of the
-    bucket-sort launch (csrc/sort_tables.hip: RowsJob) and the row builder runs its q and k roles only.  Shapes that
+    bucket-sort launch (csrc/rows_rider.h: RowsJob) and the row builder runs its q and k roles only.  Shapes that
     stress the riders' tiling: a point count that is not a multiple of their 8-point tile, another head count (the
     generic row builder), head dimensions whose 16-bit rows end inside a 16-byte piece (D = 20) or early (D = 8, 16)."""
     from hept_amd.synthetic import make_inputs

@@ -84,8 +84,17 @@ def test_two_role_sizes_take_both_branches_of_prep_wgs():
     assert [rs.prep_wgs(n, 2) for n in rs.TWO_ROLE_N] == [341, 342, 512, 257, 342]     # as wanted | even trips (2, 3)
     assert [rs.prep_wgs(n, 3) for n in rs.TWO_ROLE_N] == [341, 341, 341, 341, 341]
     cases = rs.two_role_cases()
+    column_d = [x for x in cases if x[1] in rs.TWO_ROLE_COLUMN_D]
+    cases = [x for x in cases if x[1] not in rs.TWO_ROLE_COLUMN_D]
     assert len(cases) == 16 and sum(1 for n, hdc, p in cases if hdc != (8, 24, 6)) == 1
-    for n, hdc, p in cases:
+    # the riders' column-D cases: every shape in every tile type, accepted by the library's own shape check
+    assert sorted(column_d) == sorted((10912, hdc, p) for hdc in ((3, 4, 3), (3, 20, 4)) for p in ("fp32", "bf16", "mixed16"))
+    from hept_amd import _lib
+    for n, (h, d, c), p in column_d:
+        s = rs.two_role_shape(n, (h, d, c))
+        assert _lib.load().hept_check_shape(n, h, d, c, s.T, s.B) == 0, (n, h, d, c)
+    assert _lib.load().hept_check_shape(10912, 8, 28, 2, 2, 32) != 0         # D = 28: no shape the operator accepts
+    for n, hdc, p in cases + column_d:
         s = rs.two_role_shape(n, hdc)
         assert sw.n_points(s) == n and n % 32 == 0 and sw.riders(n, s.H, s.D, s.T, p, s.B), (n, hdc, p)
         assert ("rows-tuned" in sw.cells(s)) == (hdc == (8, 24, 6))
